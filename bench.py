@@ -14,6 +14,13 @@ Gaussian map (frame sharding); rank 0 broadcasts the canonical
 Gaussian set over RCCL every --bcast-every steps (inside the timed region).
 `value` = frames processed by all ranks / max-over-ranks wall time.
 
+A plain run (bench.py --gpus 1 --steps N --warmup W) sets up, warms up, times exactly N tracking iterations
+and prints the JSON line: metric / value / unit / ms_per_step and the roofline of the timed replays' own
+in-kernel clocks.  --dump-outputs DIR also writes what the last timed step left its caller as DIR/<name>.npy.
+Every other measurement -- the all-clocks stage breakdown, the unfused and drop-in legs, configs 1 and 2,
+STREAM, Fisher, mapping, sequence, the CPU baseline, the N > 1 broadcast split -- takes runs of its own and
+runs only with --full (each still selected by its own option).
+
 The JSON line carries:
   roofline      -- render-backward kernel (one dual launch per frame): SURVEY.md
                    8(d) algorithmic bytes per launch extended to both colour sets
@@ -21,7 +28,7 @@ The JSON line carries:
                    duration during the timed region, measured on its launch
                    stream: device wall-clock stamps around every launch (graph
                    mode; hipEvent records cannot be captured) or hipEvents (eager);
-  cpu_baseline  -- rank 0 at N=1 only: the float32 C oracle (oracle/) on one
+  cpu_baseline  -- --full, rank 0 at N=1 only: the float32 C oracle (oracle/) on one
                    frame of the same workload, single thread.
 """
 from __future__ import annotations
@@ -50,7 +57,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--config", type=int, default=None, help="BASELINE config (default: 3 tracking, 4 mapping)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline figure (stage breakdown, unfused leg, drop-in, "
+                         "configs 1 and 2, STREAM, Fisher, mapping, sequence, CPU baseline, the N > 1 broadcast split), "
+                         "each selected by its own option below; without --full those options select nothing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path left its caller in the last step as "
+                         "DIR/<name>.npy (float32; at most 64 MB in all, a seeded row sample of larger arrays)")
+    ap.add_argument("--config",type=int, default=None, help="BASELINE config (default: 3 tracking, 4 mapping)")
     ap.add_argument("--workload", choices=("tracking", "mapping"), default="tracking",
                     help="tracking: the headline metric (config 3); mapping: SplaTAM mapping iterations "
                          "(config 4: 1M anisotropic Gaussians, SH degree 3, 1200x680)")
@@ -137,6 +151,29 @@ def img_n_contrib_sum(img_buffer: torch.Tensor, W: int, H: int) -> int:
     off = (4 * N + 255) // 256 * 256
     nc = img_buffer[off:off + 4 * N].view(torch.int32)
     return int(nc.sum().item())
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(outdir: str, arrays: dict) -> None:
+    """--dump-outputs: every tensor of `arrays` as outdir/<name>.npy in float32.  When they exceed the 64 MB
+    budget together, each array with more rows than its share keeps a fixed seeded (sorted) sample of its rows
+    -- the same rows in every run, so two builds' dumps compare entry for entry."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in arrays.items()}
+    if sum(v.numel() * 4 for v in host.values()) > DUMP_BUDGET_BYTES:
+        share = DUMP_BUDGET_BYTES // len(host)
+        for i, (k, v) in enumerate(sorted(host.items())):
+            row = 4 * max(1, v[0].numel()) if v.dim() else 4
+            keep = share // row
+            if v.dim() and v.shape[0] > keep:
+                g = torch.Generator().manual_seed(20240 + i)
+                host[k] = v[torch.randperm(v.shape[0], generator=g)[:keep].sort().values]
+    assert sum(v.numel() * 4 for v in host.values()) <= DUMP_BUDGET_BYTES
+    for k, v in host.items():
+        np.save(os.path.join(outdir, k + ".npy"), v.numpy())
 
 
 def main():
@@ -227,7 +264,7 @@ def main():
         for i in range(steps):
             if world > 1 and args.bcast_every > 0 and i % args.bcast_every == 0:
                 sd.broadcast_map(params)           # map update -> RCCL broadcast over xGMI
-            step()
+            last_loss = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -237,7 +274,17 @@ def main():
     if tracker is not None and tracker.overflowed():
         raise SystemExit(f"binning capacity overflow during the timed replays (capacity {tracker.capacity}, "
                          f"status rows {tracker.status.cpu().tolist()}): measurement invalid")
-    elapsed = sd.max_over_ranks(t1 - t0, device=dev)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left its caller: the pose columns (the frame's column holds the best
+        # candidate written back), the last iteration's loss and, for the graph path, the best candidate
+        # (min loss, quaternion, translation) and the pose optimizer's state
+        outs = {"cam_unnorm_rots": params["cam_unnorm_rots"], "cam_trans": params["cam_trans"]}
+        if tracker is not None:
+            outs.update(loss=tracker.loss, best_candidate=tracker.adam.best, pose_adam_state=tracker.adam.state)
+        else:
+            outs.update(loss=last_loss)
+        dump_outputs(args.dump_outputs, outs)
+    elapsed =sd.max_over_ranks(t1 - t0, device=dev)
     frames = steps * world
     value = frames / elapsed
     # Per-stage breakdown: every kernel's in-kernel clock on, in a separate pass of the same frames after the
@@ -245,7 +292,8 @@ def main():
     # profiles/r9i_ab_stage_clocks.txt -- so the timed replays clock the render kernel only)
     stages_timed = {k: round(v["avg_us"], 2) for k, v in stages.items() if v["launches"]}
     stages_breakdown, stages_source = stages_timed, "the timed replays' in-kernel stage clocks"
-    if tracker is not None and args.timing and args.stage_clocks == "render" and args.stage_breakdown == "on":
+    if args.full and tracker is not None and args.timing and args.stage_clocks == "render" and \
+            args.stage_breakdown == "on":
         bt = GraphTracker(params, curr, frame, iters_per_graph=S, timing=True, fuse_pose=bool(args.fuse_pose),
                           warmup_iters=1, prime=True, prime_ms=args.settle_ms, clock_stages=profiling.CLOCK_STAGES)
         profiling.enable_timing(clock_stages=profiling.CLOCK_STAGES)
@@ -266,7 +314,7 @@ def main():
         stages_breakdown = {("render_track" if k == "render_fwd" else k): v for k, v in stages_breakdown.items()}
     # the same timed frames without the broadcast, and the broadcast alone
     bcast_split = None
-    if world > 1 and tracker is not None:
+    if args.full and world > 1 and tracker is not None:
         dist.barrier()
         torch.cuda.synchronize()
         tb0 = time.perf_counter()
@@ -338,12 +386,12 @@ def main():
                              "final_T / n_contrib and the loss gradient images stay in registers (GraphTracker: "
                              "images=False, nothing reads them after the launch); alg bytes = SURVEY 8(d)'s "
                              "dual render fwd + render bwd, which count those image writes and reads")
-        if world == 1 and args.unfused_leg == "on":
+        if args.full and world == 1 and args.unfused_leg == "on":
             roofline["unfused"] = unfused_render_leg(params, curr, frame, tracker.iters, P, W, H, Tt, N)
 
-    dropin = dropin_leg(args, scene, dev) if args.dropin == "on" else None
+    dropin = dropin_leg(args, scene, dev) if args.full and args.dropin == "on" else None
     configs = None
-    if args.configs == "on" or (args.configs == "auto" and world == 1):
+    if args.full and (args.configs == "on" or (args.configs == "auto" and world == 1)):
         configs = configs_leg(dev, want_cpu=rank == 0 and args.cpu_baseline != "off")
         stream = hbm_stream_gbs()
         if stream:
@@ -354,20 +402,20 @@ def main():
                 "source": "tools/micro/stream (1 GiB float4 arrays, best of 20 launches): grid-stride "
                           "copy / triad, and block-tile copies with 4-16 loads in flight per thread "
                           "(plain or nontemporal)"}
-    fisher = fisher_leg(args, scene, dev, world=world, rank=rank) if args.fisher == "on" else None
+    fisher = fisher_leg(args, scene, dev, world=world, rank=rank) if args.full and args.fisher == "on" else None
     mapping = None
-    if args.mapping == "on" or (args.mapping == "auto" and world == 1):
+    if args.full and (args.mapping == "on" or (args.mapping == "auto" and world == 1)):
         mapping = mapping_leg(args, dev)
         if args.dropin == "on":
             mapping["dropin"] = dropin_mapping_leg(args, dev)
 
     sequence = None
-    if args.sequence == "on" or (args.sequence == "auto" and world == 1):
+    if args.full and (args.sequence == "on" or (args.sequence == "auto" and world == 1)):
         sequence = sequence_leg(args, dev)
 
     # ---- CPU baseline: the float32 C oracle on one frame (rank 0, N=1) ------
     cpu = None
-    want_cpu = args.cpu_baseline == "on" or (args.cpu_baseline == "auto" and world == 1)
+    want_cpu = args.full and (args.cpu_baseline == "on" or (args.cpu_baseline == "auto" and world == 1))
     if want_cpu and rank == 0:
         import numpy as np
         from oracle import oracle as orc
@@ -1004,6 +1052,7 @@ def mapping_leg(args, dev):
     import copy
     a = copy.copy(args)
     a.config, a.steps, a.warmup = 4, max(1, args.mapping_steps), args.map_frame_iters
+    a.dump_outputs = None  # (--dump-outputs is the timed headline path's)
     line = run_mapping(a, 1, 0, dev)
     keep = ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "execution", "config", "roofline",
             "stages_us", "stages_source", "pruning")
@@ -1073,8 +1122,12 @@ def run_mapping(args, world, rank, dev):
     survivors = int(mapper.survivors().sum().item())
     nr = mapper.num_rendered()
     mcap, prune_iters = mapper.capacity, sorted(mapper.prune_at)
+    if args.dump_outputs and rank == 0:  # the map the last timed iteration left (pruned Gaussians: survivors 0)
+        outs = {k: params[k] for k in snap}
+        outs["survivors"] = mapper.survivors()
+        dump_outputs(args.dump_outputs, outs)
     stages_all = None
-    if args.timing and getattr(args, "stage_breakdown", "on") == "on":  # every stage clocked, one untimed frame
+    if args.full and args.timing and args.stage_breakdown == "on":  # every stage clocked, one untimed frame
         del mapper
         with torch.no_grad():
             for k, v in snap.items():

@@ -18,7 +18,7 @@ def test_bench_two_ranks(cuda):
     env = dict(os.environ, GSR_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", "--master-port=29517", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-           "--steps", "40", "--warmup", "5", "--bcast-every", "40", "--dropin", "off", "--fisher", "off",
+           "--full", "--steps", "40", "--warmup", "5", "--bcast-every", "40", "--dropin", "off", "--fisher", "off",
            "--mapping", "off", "--cpu-baseline", "off"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

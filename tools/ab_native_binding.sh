@@ -1,7 +1,7 @@
 set -e
 OUT=gpurun_out/r8d; mkdir -p $OUT
 for r in 1 2; do for v in 0 1; do
-  GSR_NATIVE_BINDING=$v timeout -k 10 400 python bench.py --cpu-baseline off --fisher off --mapping off --configs off --unfused-leg off > $OUT/nat_${v}_$r.log 2>&1
+  GSR_NATIVE_BINDING=$v timeout -k 10 400 python bench.py --full --cpu-baseline off --fisher off --mapping off --configs off --unfused-leg off > $OUT/nat_${v}_$r.log 2>&1
   python - $OUT/nat_${v}_$r.log $v $r <<'PY'
 import json, sys
 b = [json.loads(l) for l in open(sys.argv[1]) if l.startswith("{")][-1]

@@ -5,8 +5,8 @@
 # Usage: tools/gpu_round.sh TAG step...
 #   tests            the GPU suite (pytest -m gpu)
 #   smoke            __graft_entry__.smoke()
-#   bench            the bench line without the slow legs (drop-in, CPU baseline off)
-#   full             the default bench line exactly as the driver runs it
+#   bench            the --full bench line without the slow legs (drop-in, CPU baseline off)
+#   full             the whole bench line (bench.py --full: every leg beside the headline)
 #   map              the mapping bench leg alone (config 4)
 #   prof             rocprofv3 kernel trace + stats of the headline bench (tracking legs only)
 #   pmc              FETCH_SIZE / WRITE_SIZE passes (one rocprofv3 run per counter) of the headline bench
@@ -52,10 +52,10 @@ for s in "$@"; do
              > "$OUT/tests.log" 2>&1 || { echo "tests failed"; tail -40 "$OUT/tests.log"; exit 1; } ;;
     smoke) timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 \
              || { echo "smoke failed"; tail -20 "$OUT/smoke.log"; exit 1; } ;;
-    bench) timeout -k 10 300 python bench.py --dropin off --cpu-baseline off > "$OUT/bench.log" 2>&1 \
+    bench) timeout -k 10 300 python bench.py --full --dropin off --cpu-baseline off > "$OUT/bench.log" 2>&1 \
              || { echo "bench failed"; tail -30 "$OUT/bench.log"; exit 1; } ;;
-    full) timeout -k 10 500 python bench.py > "$OUT/full.log" 2>&1 || { echo "full bench failed"; tail -30 "$OUT/full.log"; exit 1; } ;;
-    map) timeout -k 10 300 python bench.py --workload mapping --cpu-baseline off > "$OUT/map.log" 2>&1 \
+    full) timeout -k 10 500 python bench.py --full > "$OUT/full.log" 2>&1 || { echo "full bench failed"; tail -30 "$OUT/full.log"; exit 1; } ;;
+    map) timeout -k 10 300 python bench.py --full --workload mapping --cpu-baseline off > "$OUT/map.log" 2>&1 \
              || { echo "map failed"; tail -30 "$OUT/map.log"; exit 1; } ;;
     prof) ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run \
              --output-format csv -- python "$ROOT/bench.py" --steps 40 --warmup 20 $LIGHT > "$OUT/prof.log" 2>&1 ) \
@@ -67,23 +67,23 @@ for s in "$@"; do
                || { echo "pmc $C failed"; tail -20 "$OUT/pmc_$C.log"; exit 1; }
          done ;;
     mprof) ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/mprof" -o run \
-             --output-format csv -- python "$ROOT/bench.py" --workload mapping --cpu-baseline off --dropin off \
+             --output-format csv -- python "$ROOT/bench.py" --full --workload mapping --cpu-baseline off --dropin off \
              > "$OUT/mprof.log" 2>&1 ) || { echo "mprof failed"; tail -20 "$OUT/mprof.log"; exit 1; } ;;
-    mpmc) timeout -k 10 300 python bench.py --workload mapping --cpu-baseline off > "$OUT/map.log" 2>&1 \
+    mpmc) timeout -k 10 300 python bench.py --full --workload mapping --cpu-baseline off > "$OUT/map.log" 2>&1 \
              || { echo "map failed"; tail -30 "$OUT/map.log"; exit 1; }
          for C in FETCH_SIZE WRITE_SIZE; do
            ( cd /tmp && export TMPDIR=/tmp && timeout -s KILL 240 rocprofv3 --pmc $C \
                --kernel-include-regex 'render_|gauss_bwd' -T -d "$OUT/pmc_map_$C" -o run --output-format csv \
-               -- python "$ROOT/bench.py" --workload mapping --steps 5 --warmup 5 --cpu-baseline off \
+               -- python "$ROOT/bench.py" --full --workload mapping --steps 5 --warmup 5 --cpu-baseline off \
                > "$OUT/pmc_map_$C.log" 2>&1 ) || { echo "pmc map $C failed"; tail -20 "$OUT/pmc_map_$C.log"; exit 1; }
          done ;;
     mpmcab) for B in culled reference; do  # tile cull A/B of the mapping kernels: times + FETCH / WRITE bytes
-           timeout -k 10 300 python bench.py --workload mapping --cpu-baseline off --map-binning $B \
+           timeout -k 10 300 python bench.py --full --workload mapping --cpu-baseline off --map-binning $B \
                > "$OUT/map_$B.log" 2>&1 || { echo "map $B failed"; tail -30 "$OUT/map_$B.log"; exit 1; }
            for C in FETCH_SIZE WRITE_SIZE; do
              ( cd /tmp && export TMPDIR=/tmp && timeout -s KILL 240 rocprofv3 --pmc $C \
                  --kernel-include-regex 'render_|gauss_bwd' -T -d "$OUT/pmc_map_${B}_$C" -o run --output-format csv \
-                 -- python "$ROOT/bench.py" --workload mapping --steps 5 --warmup 5 --cpu-baseline off --map-binning $B \
+                 -- python "$ROOT/bench.py" --full --workload mapping --steps 5 --warmup 5 --cpu-baseline off --map-binning $B \
                  > "$OUT/pmc_map_${B}_$C.log" 2>&1 ) || { echo "pmc map $B $C failed"; tail -20 "$OUT/pmc_map_${B}_$C.log"; exit 1; }
            done
          done ;;
@@ -108,7 +108,7 @@ for s in "$@"; do
         for G in "$G1" "$G2" FETCH_SIZE WRITE_SIZE; do
           i=$((i+1))
           ( cd /tmp && export TMPDIR=/tmp && timeout -s KILL 240 rocprofv3 --pmc $G --kernel-include-regex "$RX" -T \
-              -d "$OUT/msq$i" -o run --output-format csv -- python "$ROOT/bench.py" --workload mapping --steps 5 --warmup 5 \
+              -d "$OUT/msq$i" -o run --output-format csv -- python "$ROOT/bench.py" --full --workload mapping --steps 5 --warmup 5 \
               --cpu-baseline off > "$OUT/msq$i.log" 2>&1 ) || { echo "msq pass $i failed"; tail -20 "$OUT/msq$i.log"; exit 1; }
         done ;;
     sq|sq=*) RX='render_'; [ "$s" != sq ] && RX=${s#sq=}
@@ -165,7 +165,7 @@ PY
            for t in $L; do
              d="$OUT/mabprof_${t}_$r"
              ( cd /tmp && export TMPDIR=/tmp && GSR_LIB_AB=1 GSR_LIB=$(lib_of $t) timeout -k 10 300 rocprofv3 --kernel-trace --stats \
-                 -d "$d" -o run --output-format csv -- python "$ROOT/bench.py" --workload mapping --steps 120 --warmup 60 \
+                 -d "$d" -o run --output-format csv -- python "$ROOT/bench.py" --full --workload mapping --steps 120 --warmup 60 \
                  --cpu-baseline off > "$d.log" 2>&1 ) || { echo "mabprof $t failed"; tail -20 "$d.log"; exit 1; }
              python - "$d" $t $r <<'PY' | tee -a "$OUT/mabprof.txt"
 import csv, glob, json, sys
@@ -184,7 +184,7 @@ PY
            L="base ${TAGS//,/ }"; [ $r = 2 ] && L="$(echo $L | tr ' ' '\n' | tac | tr '\n' ' ')"
            for t in $L; do
              f="$OUT/seqab_${t}_$r.log"
-             GSR_LIB_AB=1 GSR_LIB=$(lib_of $t) timeout -k 10 300 python bench.py $LIGHT --sequence on > "$f" 2>&1 \
+             GSR_LIB_AB=1 GSR_LIB=$(lib_of $t) timeout -k 10 300 python bench.py --full $LIGHT --sequence on > "$f" 2>&1 \
                  || { echo "seqab $t failed"; tail -20 "$f"; exit 1; }
              python -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])['sequence']; print('seqab', sys.argv[2], 'round', sys.argv[3], 'frames/s', d['value'], 'phases', d['phases_ms'], 'per_frame', d['per_frame']['value'])" "$f" $t $r | tee -a "$OUT/seqab.txt"
            done
@@ -195,7 +195,7 @@ PY
            for t in $L; do
              d="$OUT/abfisher_${t}_$r"
              ( cd /tmp && export TMPDIR=/tmp && GSR_LIB_AB=1 GSR_LIB=$(lib_of $t) timeout -k 10 300 rocprofv3 --kernel-trace --stats \
-                 -d "$d" -o run --output-format csv -- python "$ROOT/bench.py" --steps 20 --warmup 5 --cpu-baseline off \
+                 -d "$d" -o run --output-format csv -- python "$ROOT/bench.py" --full --steps 20 --warmup 5 --cpu-baseline off \
                  --dropin off --mapping off --configs off --unfused-leg off > "$d.log" 2>&1 ) \
                  || { echo "abfisher $t failed"; tail -20 "$d.log"; exit 1; }
              python - "$d" $t $r <<'PY' | tee -a "$OUT/abfisher.txt"
@@ -214,7 +214,7 @@ PY
             [ $r = 2 ] && ORDER=$(echo $ORDER | tr ' ' '\n' | tac | tr '\n' ' ')  # round 2 in reverse order
             for t in $ORDER; do
               f="$OUT/abbench_${t}_$r.log"
-              GSR_LIB_AB=1 GSR_LIB=$(lib_of $t) timeout -k 10 300 python bench.py --cpu-baseline off --dropin off --fisher off \
+              GSR_LIB_AB=1 GSR_LIB=$(lib_of $t) timeout -k 10 300 python bench.py --full --cpu-baseline off --dropin off --fisher off \
                   --configs off --unfused-leg off > "$f" 2>&1 || { echo "abbench $t failed"; tail -20 "$f"; exit 1; }
               python - "$f" $t $r <<'PY' | tee -a "$OUT/abbench.txt"
 import json, sys
@@ -230,7 +230,7 @@ PY
             [ $r = 2 ] && ORDER=$(echo $ORDER | tr ' ' '\n' | tac | tr '\n' ' ')
             for t in $ORDER; do
               f="$OUT/abdropin_${t}_$r.log"
-              GSR_LIB_AB=1 GSR_LIB=$(lib_of $t) timeout -k 10 400 python bench.py --cpu-baseline off --fisher off --mapping off \
+              GSR_LIB_AB=1 GSR_LIB=$(lib_of $t) timeout -k 10 400 python bench.py --full --cpu-baseline off --fisher off --mapping off \
                   --configs off --unfused-leg off > "$f" 2>&1 || { echo "abdropin $t failed"; tail -20 "$f"; exit 1; }
               python - "$f" $t $r <<'PY' | tee -a "$OUT/abdropin.txt"
 import json, sys
