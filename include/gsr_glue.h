@@ -37,11 +37,20 @@
 extern "C" {
 #endif
 
-/* Scratch floats needed by gsr_track_transform_bwd(_adam) (n = P) and
- * gsr_track_l1_fwd(_bwd) (n = H*W): per-workgroup partials followed by an
- * arrival counter.  The scratch must be zero-filled before its first use; every
- * call leaves it zero-filled, so one buffer serves any number of calls on one
- * stream (not calls running concurrently). */
+/* Reduction scratch -- one contract for every `scratch` argument of this header
+ * (gsr_track_transform_bwd(_adam), gsr_track_l1_fwd(_bwd), gsr_track_forward_*_static*,
+ * gsr_track_backward_dual(_records), gsr_map_loss_fwd):
+ *   - layout: the arrival counters are the scratch's first 272 32-bit words, whatever the
+ *     call's sizes; the call's per-workgroup partial sums follow them;
+ *   - the caller zero-fills the buffer once, before its first use.  Every call returns the
+ *     counters to zero and overwrites the partials it reads; the partials are NOT left zero
+ *     (nothing reads them before they are rewritten);
+ *   - so any buffer of at least the call's *_scratch_floats() size serves any number of calls
+ *     of any of these entry points, in any order, on one stream -- e.g. one buffer of the
+ *     largest size for all of them.  Calls that may run concurrently (other streams, parallel
+ *     graph branches) need buffers of their own.
+ * Scratch floats needed by gsr_track_transform_bwd(_adam) (n = P) and
+ * gsr_track_l1_fwd(_bwd) (n = H*W): */
 int gsr_track_scratch_floats(int n);
 
 /* cam_q: the frame's unnormalised (w,x,y,z) quaternion, element k at cam_q[k * q_stride]
@@ -118,8 +127,9 @@ int gsr_track_l1_bwd(int H, int W, const float* im, const float* depth_sil, cons
  * its gradient images dL_dim [3,H,W] / dL_ddepth_sil [3,H,W] are written without
  * reading the rendered images back; dL_dloss (device scalar, the caller's static
  * loss seed) is read when the kernel runs.  scratch:
- * gsr_track_forward_scratch_floats(W, H) floats, zero-filled before first use, left
- * zero-filled.  The loss is valid iff the status reports no overflow. */
+ * gsr_track_forward_scratch_floats(W, H) floats (the reduction scratch contract above:
+ * zero-filled before first use, counters left zero).  The loss is valid iff the status
+ * reports no overflow. */
 int gsr_track_forward_scratch_floats(int image_width, int image_height);
 int gsr_track_forward_dual_static(const gsr_settings* settings, const gsr_gaussians* gaussians, const float* colors2,
                                   int capacity, unsigned* status, float* out_color, float* out_color2,
@@ -174,8 +184,8 @@ int gsr_track_forward_dual_static_xf(const gsr_settings* settings, const gsr_gau
  * gaussians (camera-frame rendervars), radii, colors2 ([z,1,z^2]) and the buffers
  * are those of the gsr_forward_dual(_static) call; means_world / unnorm_rot /
  * scale_cols / cam_q / cam_t / w2c those of gsr_track_transform_fwd.  scratch:
- * gsr_track_backward_scratch_floats(P) floats, zero-filled before first use,
- * left zero-filled.  The Adam step is skipped when the forward's own device
+ * gsr_track_backward_scratch_floats(P) floats (the reduction scratch contract above:
+ * zero-filled before first use, counters left zero).  The Adam step is skipped when the forward's own device
  * counters show an overflow of num_rendered (its capacity); `track` (may be
  * NULL) adds the best-candidate selection (its status / capacity are not used).
  * log_scales [P, scale_cols] (may be NULL): recompute each Gaussian's camera-frame mean, rotation
@@ -233,8 +243,10 @@ int gsr_track_backward_dual_records(const gsr_settings* settings, const gsr_gaus
  * depth 1.0), and the mapping optimizer (splatam.py:166-172).  Forward of the
  * transform is gsr_track_transform_fwd (identical outputs). */
 
-/* Persistent zero-filled scratch (same contract as gsr_track_scratch_floats)
- * and the per-call state gsr_map_loss_fwd hands to gsr_map_loss_bwd. */
+/* Scratch floats of gsr_map_loss_fwd (the reduction scratch contract at
+ * gsr_track_scratch_floats: zero-filled before first use, counters left zero, shareable
+ * with the tracking entry points) and the per-call state gsr_map_loss_fwd hands to
+ * gsr_map_loss_bwd. */
 int gsr_map_loss_scratch_floats(int H, int W);
 int gsr_map_loss_state_floats(int H, int W);
 

@@ -979,7 +979,8 @@ __device__ __forceinline__ void gauss_bwd_body(Camera cam, GaussIn g, GeomPtrs g
         }
         block_sum<POSE_PARTS>(v, s_red, s_tot);
         __syncthreads();
-        if (threadIdx.x < POSE_PARTS) st_agent(pf.part + POSE_PARTS * blockIdx.x + threadIdx.x, s_tot[threadIdx.x]);
+        float* const part = scratch_partials(pf.scratch);
+        if (threadIdx.x < POSE_PARTS) st_agent(part + POSE_PARTS * blockIdx.x + threadIdx.x, s_tot[threadIdx.x]);
         if constexpr (kAblate == 3) return;  // timing ablation: no pose tail (invalid pose update)
 #if GSR_POSE_TAIL == 1
         // One-level fixed-order sum: the last workgroup to arrive (grouped arrival counters) reads
@@ -989,7 +990,7 @@ __device__ __forceinline__ void gauss_bwd_body(Camera cam, GaussIn g, GeomPtrs g
         // round trips (publish, arrive, gather) instead of the two-level tail's six.
         {
             const int nb = gridDim.x;
-            if (!last_block_arrive_grouped(reinterpret_cast<uint32_t*>(pf.part + POSE_PARTS * nb))) return;
+            if (!last_block_arrive_grouped(scratch_counters(pf.scratch))) return;
             if constexpr (kAblate == 4) return;  // timing ablation: arrival only
             static_assert(256 % POSE_PARTS == 0, "a thread keeps one value index");
             constexpr int CH = 40;
@@ -1000,7 +1001,7 @@ __device__ __forceinline__ void gauss_bwd_body(Camera cam, GaussIn g, GeomPtrs g
 #pragma unroll
                 for (int u = 0; u < CH; u++) {
                     const int f = f0 + 256 * u;
-                    buf[u] = f < total ? ld_agent(pf.part + f) : 0.f;
+                    buf[u] = f < total ? ld_agent(part + f) : 0.f;
                 }
 #pragma unroll
                 for (int u = 0; u < CH; u++) acc += buf[u];
@@ -1029,8 +1030,8 @@ __device__ __forceinline__ void gauss_bwd_body(Camera cam, GaussIn g, GeomPtrs g
         // and publishes the group sum; the last group then adds the 16 group sums.  (One
         // workgroup reading all partials serially cost ~18 us more than the separate pose kernel.)
         const int nb = gridDim.x;
-        uint32_t* ctr = reinterpret_cast<uint32_t*>(pf.part + POSE_PARTS * nb);
-        float* gsum = pf.part + POSE_PARTS * nb + ARRIVE_GROUPED_WORDS;
+        uint32_t* ctr = scratch_counters(pf.scratch);
+        float* gsum = part + POSE_PARTS * nb;
         __shared__ uint32_t s_flag;
         const uint32_t g = (uint32_t)blockIdx.x & 15u;
         const uint32_t ngroups = nb < 16 ? (uint32_t)nb : 16u;
@@ -1049,7 +1050,7 @@ __device__ __forceinline__ void gauss_bwd_body(Camera cam, GaussIn g, GeomPtrs g
         for (int k = 0; k < POSE_PARTS; k++) v[k] = 0.f;
         for (int b = (int)g + 16 * threadIdx.x; b < nb; b += 16 * 256)
 #pragma unroll
-            for (int k = 0; k < POSE_PARTS; k++) v[k] += ld_agent(pf.part + POSE_PARTS * b + k);
+            for (int k = 0; k < POSE_PARTS; k++) v[k] += ld_agent(part + POSE_PARTS * b + k);
         __syncthreads();
         block_sum<POSE_PARTS>(v, s_red, s_tot);
         __syncthreads();
@@ -1120,7 +1121,7 @@ gauss_bwd_kernel(Camera cam, GaussIn g, GeomPtrs geo, const int* __restrict__ ra
     if constexpr (CLK) kclock_end(clk);
 }
 
-// workgroup partials, arrival counters, the 16 group sums
+// arrival counters, workgroup partials, the 16 group sums
 int pose_fuse_scratch_floats(int P) { return POSE_PARTS * ((P + 255) / 256) + ARRIVE_GROUPED_WORDS + 16 * POSE_PARTS; }
 
 hipError_t launch_gauss_bwd(const Camera& cam, const GaussIn& g, GeomPtrs geo, const int* radii, const float* inst,

@@ -917,6 +917,14 @@ __device__ __forceinline__ void gather_partials(const float* part, int stride, i
 // ~15 us).  ctr: ARRIVE_GROUPED_WORDS words, zero before the first launch.
 constexpr int ARRIVE_STRIDE = 16;
 constexpr int ARRIVE_GROUPED_WORDS = 17 * ARRIVE_STRIDE;
+// Layout of every reduction scratch (include/gsr_glue.h): the arrival counters are its first
+// ARRIVE_GROUPED_WORDS words, whatever the grid, and the partials follow.  Only the counters must
+// stay zero between launches (each launch writes the partials it reads), so users with different
+// grids can share one buffer: no user's partials ever land on another's counters.
+__host__ __device__ __forceinline__ uint32_t* scratch_counters(float* scratch) {
+    return reinterpret_cast<uint32_t*>(scratch);
+}
+__host__ __device__ __forceinline__ float* scratch_partials(float* scratch) { return scratch + ARRIVE_GROUPED_WORDS; }
 __device__ __forceinline__ bool last_block_arrive_grouped(uint32_t* ctr) {
     __shared__ uint32_t s_last2;
     __builtin_amdgcn_s_waitcnt(0x0F70);  // s_waitcnt vmcnt(0)
@@ -1261,7 +1269,7 @@ struct TrackL1 {
     const float* seed;      // dL/dloss (device scalar, read when the kernel runs)
     float* dL_dim;          // [3,H,W]
     float* dL_dds;          // [3,H,W] (channels 1, 2 written as zero)
-    float* part;            // zero-filled scratch: 2 partials per tile + arrival counters
+    float* scratch;         // arrival counters (zero between launches), then 2 partials per tile
     float* loss;            // device scalar
 };
 int track_l1_fused_scratch_floats(int ntiles);
@@ -1334,7 +1342,7 @@ struct PoseFuse {
     float* cam_t;              // frame's translation column (stride qs)
     int qs;
     const float* w2c;          // [16] row-major, depth colours
-    float* part;               // zero-filled scratch: 16 * nblocks partials + arrival counters
+    float* scratch;            // arrival counters (zero between launches), 16 * nblocks partials, group sums
     float* adam_state;         // 15 floats (nullptr: write dq / dt instead)
     double lr_q, lr_t, beta1, beta2, eps;
     float* dq;                 // gradient outputs when adam_state == nullptr

@@ -50,13 +50,13 @@ track_transform_fwd_kernel(int P, const float* __restrict__ mw, const float* __r
 // Pose gradient in one launch: every workgroup publishes its partial of the 16
 // sums (sum g, sum g p^T, sum dquat_mult^T dr); the last one to arrive adds the
 // partials in a fixed order (bitwise reproducible) and runs pose_fin.
-// scratch: 16 * gridDim.x partials, then the arrival counters (zero before the
-// first launch; every launch leaves them zero).
+// scratch: the arrival counters (zero before the first launch; every launch
+// leaves them zero), then 16 * gridDim.x partials.
 __global__ void __launch_bounds__(GLUE_BLOCK)
 track_transform_bwd_kernel(int P, const float* __restrict__ mw, const float* __restrict__ ur, int scols,
                            const float* __restrict__ cq, int qs, const float* __restrict__ mc,
                            const float* __restrict__ w2c, const float* __restrict__ gm,
-                           const float* __restrict__ gr, const float* __restrict__ gd, float* __restrict__ part,
+                           const float* __restrict__ gr, const float* __restrict__ gd, float* __restrict__ scratch,
                            float* dq, float* dt, PoseAdam adam) {
     __shared__ float s_red[4 * POSE_PARTS];
     __shared__ float s_tot[POSE_PARTS];
@@ -75,9 +75,10 @@ track_transform_bwd_kernel(int P, const float* __restrict__ mw, const float* __r
     }
     block_sum<POSE_PARTS>(v, s_red, s_tot);
     __syncthreads();
+    float* const part = scratch_partials(scratch);
     if (threadIdx.x < POSE_PARTS) st_agent(part + POSE_PARTS * blockIdx.x + threadIdx.x, s_tot[threadIdx.x]);
     const int nb = gridDim.x;
-    if (!last_block_arrive_grouped(reinterpret_cast<uint32_t*>(part + POSE_PARTS * nb))) return;
+    if (!last_block_arrive_grouped(scratch_counters(scratch))) return;
     // last workgroup: fixed-order sum of the partials
 #pragma unroll
     for (int k = 0; k < POSE_PARTS; k++) v[k] = 0.f;
@@ -91,12 +92,12 @@ track_transform_bwd_kernel(int P, const float* __restrict__ mw, const float* __r
 // Masked L1 loss in one launch: per-workgroup partial sums published, the last
 // workgroup adds them in a fixed order and writes the loss.  With dloss, the
 // gradient images are written in the same pass (g = *dloss, read now: the
-// caller's loss seed must already hold its value).  scratch: 4 * gridDim.x
-// partials, then the arrival counter (zero before the first launch; left zero).
+// caller's loss seed must already hold its value).  scratch: the arrival counters
+// (zero before the first launch; left zero), then 4 * gridDim.x partials.
 __global__ void __launch_bounds__(GLUE_BLOCK)
 track_l1_kernel(int HW, const float* __restrict__ im, const float* __restrict__ ds,
                 const float* __restrict__ gt_im, const float* __restrict__ gt_d, float thres, float w_im,
-                float w_depth, float* __restrict__ part, float* __restrict__ loss, const float* __restrict__ dloss,
+                float w_depth, float* __restrict__ scratch, float* __restrict__ loss, const float* __restrict__ dloss,
                 float* __restrict__ dim, float* __restrict__ dds) {
     __shared__ float s_red[4 * 4];
     __shared__ float s_tot[4];
@@ -120,9 +121,10 @@ track_l1_kernel(int HW, const float* __restrict__ im, const float* __restrict__ 
     }
     block_sum<4>(v, s_red, s_tot);
     __syncthreads();
+    float* const part = scratch_partials(scratch);
     if (threadIdx.x < 2) st_agent(part + 4 * blockIdx.x + threadIdx.x, s_tot[threadIdx.x]);
     const int nb = gridDim.x;
-    if (!last_block_arrive_grouped(reinterpret_cast<uint32_t*>(part + 4 * nb))) return;
+    if (!last_block_arrive_grouped(scratch_counters(scratch))) return;
     v[0] = v[1] = v[2] = v[3] = 0.f;
     {
         float v2[2] = {0.f, 0.f};
@@ -191,7 +193,7 @@ using namespace gsr;
 
 extern "C" {
 
-// partials of the widest reduction + the arrival counters (the L1 needs 4 per workgroup)
+// the arrival counters + partials of the widest reduction (the L1 needs 4 per workgroup)
 int gsr_track_scratch_floats(int n) { return POSE_PARTS * blocks_for(n) + ARRIVE_GROUPED_WORDS; }
 
 int gsr_track_transform_fwd(int P, const float* means_world, const float* unnorm_rot, const float* logit_opac,

@@ -152,13 +152,13 @@ __device__ __forceinline__ void vertical_pass(const float (*hs)[TH + 2 * SS_R][S
     }
 }
 
-// gmap: 3 partial maps x 3 channels x HW floats; part: MAP_PARTS * nblocks
-// partials then the arrival counters; out: [0] depth mask count (read by the backward).
+// gmap: 3 partial maps x 3 channels x HW floats; scratch: the arrival counters then
+// MAP_PARTS * nblocks partials; out: [0] depth mask count (read by the backward).
 template <int TH>
 __global__ void __launch_bounds__(SS_BLOCK)
 map_loss_fwd_kernel(int H, int W, const float* __restrict__ im, const float* __restrict__ ds,
                     const float* __restrict__ gt_im, const float* __restrict__ gt_d, float w_im, float w_depth,
-                    Window win, float* __restrict__ gmap, float* __restrict__ part, float* __restrict__ out,
+                    Window win, float* __restrict__ gmap, float* __restrict__ scratch, float* __restrict__ out,
                     float* __restrict__ loss) {
     constexpr int SS_TH = TH, SS_IH = TH + 2 * SS_R, SS_ROWS_PER_THREAD = TH / (SS_BLOCK / SS_TW);
     __shared__ float s_in[2][SS_IH][SS_IW];
@@ -224,8 +224,9 @@ map_loss_fwd_kernel(int H, int W, const float* __restrict__ im, const float* __r
     __syncthreads();
     const int nb = gridDim.x * gridDim.y * gridDim.z;
     const int b = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    float* const part = scratch_partials(scratch);
     if (threadIdx.x < MAP_PARTS) st_agent(part + MAP_PARTS * b + threadIdx.x, s_tot[threadIdx.x]);
-    if (!last_block_arrive_grouped(reinterpret_cast<uint32_t*>(part + MAP_PARTS * nb))) return;
+    if (!last_block_arrive_grouped(scratch_counters(scratch))) return;
 #pragma unroll
     for (int k = 0; k < MAP_PARTS; k++) v[k] = 0.f;
     gather_partials<MAP_PARTS, 8>(part, MAP_PARTS, nb, threadIdx.x, SS_BLOCK, v);

@@ -431,11 +431,11 @@ __device__ __forceinline__ void l1_finish(const TrackL1& l1) {
     __shared__ float s_fin[16];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, row4 = lane >> 4;
     const int nb = gridDim.x * gridDim.y;
-    if (last_block_arrive_grouped(reinterpret_cast<uint32_t*>(l1.part + 2 * nb))) {
+    if (last_block_arrive_grouped(scratch_counters(l1.scratch))) {
         float v[4] = {0.f, 0.f, 0.f, 0.f}, r[1];
         {
             float v2[2] = {0.f, 0.f};
-            gather_partials<2, GSR_L1_CH>(l1.part, 2, nb, tid, TILE_PIX, v2);
+            gather_partials<2, GSR_L1_CH>(scratch_partials(l1.scratch), 2, nb, tid, TILE_PIX, v2);
             v[0] = v2[0];
             v[1] = v2[1];
         }
@@ -551,7 +551,7 @@ __device__ __forceinline__ void fwd_epilogue(const Camera& cam, int tile, const 
         __syncthreads();
         if (tid < 4) s_tot[tid] = (s_red[tid] + s_red[4 + tid]) + (s_red[8 + tid] + s_red[12 + tid]);
         __syncthreads();
-        if (tid < 2) st_agent(l1.part + 2 * tile + tid, s_tot[tid]);
+        if (tid < 2) st_agent(scratch_partials(l1.scratch) + 2 * tile + tid, s_tot[tid]);
         if (L1_FINISH) l1_finish(l1);
     }
 }

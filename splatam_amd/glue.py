@@ -94,9 +94,11 @@ _SCRATCH: dict = {}
 
 
 def _scratch(t: torch.Tensor, n: int) -> torch.Tensor:
-    """Zero-filled scratch for the glue reductions (gsr_track_scratch_floats): the kernels
-    leave it zero-filled, so one persistent buffer per (device, stream, size) serves every
-    call issued on that stream (calls on one stream never overlap)."""
+    """Scratch for the glue reductions (include/gsr_glue.h, "Reduction scratch"): zero-filled once,
+    here.  Every kernel keeps its arrival counters in the buffer's first 272 words and returns them
+    to zero; the partial sums behind them are left as written (each call overwrites the ones it
+    reads).  So one persistent buffer per (device, stream, size) serves every call issued on that
+    stream, whichever of the reductions asks for that size (calls on one stream never overlap)."""
     dev = t.device
     key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, int(n))
     buf = _SCRATCH.get(key)
