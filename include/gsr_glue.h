@@ -380,6 +380,50 @@ int gsr_points_to_camera(int P, const float* means, const float* w2c, float* pts
 int gsr_fisher_accumulate(int P, const float* dmeans3D, const float* dopacity, const float* weight, float* H,
                           void* stream);
 
+/* ------------------------------------------------------- keyframe selection --
+ * SplaTAM's overlap keyframe selection (utils/keyframe_selection.py, scripts/splatam.py:820-837)
+ * without a host read: everything is enqueued on `stream` (three launches), every input but the
+ * sizes is read on the device when the kernels run, so the call can be captured in a graph and
+ * replayed after the depth, the poses and the random words changed in place.
+ *
+ * Inputs: depth [H,W] (H <= 4096); fx, fy, cx, cy; w2c: the current frame's world-to-camera matrix
+ * (16 floats, row-major); kf_w2c [n_kf,16]: the keyframes' est_w2c; kf_time [n_kf]: their time
+ * indices; u_pix [S], perm_key [n_kf - 1] (or longer), u_draw [n_draws]: random 32-bit words;
+ * cur_row: the bank row of the current frame (>= n_kf; keyframe i is bank row i); k_select <= 1022.
+ *   1. sample: n_valid = #(depth > 0); sample j takes the valid pixel of row-major rank
+ *      r_j = (u_pix[j] * n_valid) >> 32 (64-bit product) -- where the reference draws
+ *      torch.randint(n_valid), whose bound only the device knows.  n_valid == 0: no points.
+ *   2. back-project: x = (col - cx) / fx * z, y = (row - cy) / fy * z; world point
+ *      w_a = R[0][a] x + R[1][a] y + R[2][a] z + t'_a, t'_a = -(R[0][a] t_0 + R[1][a] t_1 + R[2][a] t_2):
+ *      the rigid inverse of w2c in closed form (the reference: torch.inverse).  Every product and
+ *      sum is rounded on its own, sums left to right.
+ *   3. drop: every sample whose rank another sample drew too (the reference's unique(...,
+ *      return_counts) drops all copies), and a sample with rint(1e4 w_a) == 0 for all three a.
+ *      Deliberate difference: the reference also drops two DISTINCT pixels whose points share a
+ *      1e-4 m cell; they are kept here.
+ *   4. project into every candidate (keyframes 0 .. n_kf - 2): p = est_w2c[:3] . (w, 1) (left to
+ *      right), zz = p.z + 1e-5, u = (fx p.x + cx p.z) / zz, v = (fy p.y + cy p.z) / zz; inside when
+ *      20 < u < W - 20, 20 < v < H - 20 and zz > 0.
+ *   5. eligible: overlap > 0.  The window is the first min(k_select, #eligible) eligible
+ *      candidates in ascending (perm_key[i], i) order -- a uniformly random subset, the
+ *      reference's np.random.permutation(...)[:k] -- then keyframe n_kf - 1 if n_kf > 0, then cur_row.
+ *   6. draw i picks window[(u_draw[i] * n_window) >> 32].
+ * Outputs: overlap [n_kf - 1] kept samples inside each candidate; n_points [1] samples kept by 3;
+ * window [k_select + 2] bank rows (unused entries -1) and n_window [1]; draw_rows / draw_times
+ * [n_draws] (int64, torch.index_select indices): the drawn bank row and its time index (time_idx
+ * for cur_row); sampled_pixels [S] (may be NULL): each sample's pixel row * W + col (-1: none).
+ * workspace: gsr_keyframe_workspace_bytes(H, S) bytes of its own (not the reduction scratch above),
+ * 16-byte aligned, zero-filled once before its first use: its arrival counters (the first 16
+ * words, whatever the sizes) return to zero and everything else is written before it is read, so
+ * one buffer of the largest size serves any number of calls on one stream. */
+size_t gsr_keyframe_workspace_bytes(int H, int S);
+int gsr_keyframe_select(int H, int W, const float* depth, float fx, float fy, float cx, float cy, const float* w2c,
+                        const float* kf_w2c, int n_kf, int k_select, int S, const unsigned* u_pix,
+                        const unsigned* perm_key, int n_draws, const unsigned* u_draw, const long long* kf_time,
+                        long long time_idx, int cur_row, void* workspace, int* overlap, int* n_points, int* window,
+                        int* n_window, long long* draw_rows, long long* draw_times, int* sampled_pixels,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,9 @@ np.random.RandomState) and gathers the drawn keyframes' target image, depth and
 camera pose into per-iteration slots the captured iterations read (three gathers
 per replay, enqueued before it; the keyframes must share one camera settings object,
 one w2c and one image size -- otherwise the sequence drawn at construction is baked
-into the graph, `redraw` False).  `sequence` is the last replay's draw.
+into the graph, `redraw` False).  `sequence` is the last replay's draw.  The draws can also come from the
+device (run(device_sequence=...) after set_keyframe_bank(): the same gathers from a device-resident keyframe
+bank with device-resident indices -- splatam_amd.keyframes' overlap selection -- and no host-built index).
 Each replay is one frame's mapping.  An iteration whose forward overflows the
 binning capacity skips its Adam step on the device (its status row, sticky
 across replays, reports it).
@@ -210,6 +212,28 @@ class GraphMapper:
                                out=self._slot_params["cam_unnorm_rots"])
             torch.index_select(p["cam_trans"].detach(), -1, self._idx_dev[1], out=self._slot_params["cam_trans"])
 
+    def set_keyframe_bank(self, im: torch.Tensor, depth: torch.Tensor):
+        """A device-resident keyframe bank (splatam_amd.keyframes.KeyframeBank: im [rows, 3, H, W], depth
+        [rows, 1, H, W]) for run(device_sequence=...), whose draws index its rows on the device.  Needs the
+        redraw form; the rows must have the image size of the keyframes the mapper was built with."""
+        if not self.redraw:
+            raise RuntimeError("set_keyframe_bank needs the redraw form (keyframes sharing cam / w2c / image size)")
+        if im.shape[1:] != self._slot_im.shape[1:] or depth.shape[1:] != self._slot_depth.shape[1:] or \
+                im.shape[0] != depth.shape[0] or im.device != self._slot_im.device or \
+                im.dtype != self._slot_im.dtype or depth.dtype != self._slot_depth.dtype:
+            raise RuntimeError("set_keyframe_bank: rows of the mapper's image / depth shape on its device")
+        self._bank_im, self._bank_depth = im.contiguous(), depth.contiguous()
+
+    def _load_device(self, rows: torch.Tensor, time_ids: torch.Tensor):
+        """_load from device-resident draws: the same four gathers, from the bank, with no host-built index
+        (rows: the bank row of every iteration, time_ids: its pose column; int64 [iters] on the device)."""
+        with torch.no_grad():
+            torch.index_select(self._bank_im, 0, rows, out=self._slot_im)
+            torch.index_select(self._bank_depth, 0, rows, out=self._slot_depth)
+            p = self.params
+            torch.index_select(p["cam_unnorm_rots"].detach(), -1, time_ids, out=self._slot_params["cam_unnorm_rots"])
+            torch.index_select(p["cam_trans"].detach(), -1, time_ids, out=self._slot_params["cam_trans"])
+
     def _iteration(self, k: int):
         if self.redraw:
             kf, params, t = self._slot_kfs[k], self._slot_params, k
@@ -283,9 +307,11 @@ class GraphMapper:
         self.stale = True
         return out, m, v
 
-    def run(self, check: bool = True, sequence=None):
+    def run(self, check: bool = True, sequence=None, device_sequence=None):
         """Enqueue one frame's mapping (one graph launch).  With `redraw` the keyframe of every iteration
-        is drawn now (splatam.py:851; `sequence` overrides the draw) and gathered into the slots.  An
+        is drawn now (splatam.py:851; `sequence` overrides the draw) and gathered into the slots;
+        `device_sequence` = (rows, time_ids), int64 [iters] device tensors, takes the draws from the device
+        instead (rows of set_keyframe_bank's bank and their pose columns; `sequence` is then None).  An
         iteration whose forward overflowed skips its Adam step, and so does every later iteration of the
         frame (MapAdam.halted_word, sticky on the device), so the parameters are those of the last good
         iteration and no step uses mismatched bias corrections.  `check` (the default) ends the replay
@@ -294,7 +320,16 @@ class GraphMapper:
         afterwards."""
         if self.stale:
             raise RuntimeError("this mapper was compacted (P changed): build a new one for the next frame")
-        if self.redraw:
+        if device_sequence is not None:
+            if sequence is not None or not self.redraw or getattr(self, "_bank_im", None) is None:
+                raise RuntimeError("device_sequence: needs set_keyframe_bank() and no host `sequence`")
+            rows, time_ids = device_sequence
+            dev = self._slot_im.device
+            if any(t.dtype != torch.int64 or t.device != dev or t.shape != (self.iters,) for t in (rows, time_ids)):
+                raise ValueError(f"device_sequence: two int64 [{self.iters}] tensors on {dev}")
+            self.sequence = None
+            self._load_device(rows, time_ids)
+        elif self.redraw:
             n = len(self.keyframes)
             seq = [int(self.rng.randint(0, n)) for _ in range(self.iters)] if sequence is None else \
                 [int(j) for j in sequence]

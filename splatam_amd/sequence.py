@@ -17,9 +17,22 @@ After a frame's pruning, compact_static moves the live rows to the front in orde
 a reallocation), so the padded map's live rows are always the reference map's rows in its order; the sequence
 raises (check()) when the capacity is exhausted.  The tracker renders
 from a one-column pose slot and slot targets that each frame fills; the mapper draws from a keyframe window
-set per frame (GraphMapper.set_keyframes).  Keyframe selection is the window of the last `window - 1` keyframes
-plus the current frame (keyframe_selection_overlap, :820-836, ranks keyframes by the overlap of a random
-pixel sample -- control logic outside the rasterizer path, not restated).
+set per frame (GraphMapper.set_keyframes).
+
+Two keyframe policies (`keyframe_policy`):
+* "window" (the default): the last `window - 1` keyframes plus the current frame; frame 0 and every
+  keyframe_every-th frame are keyframes.  The draws are window indices from the sequence's numpy stream.
+* "overlap": SplaTAM's own selection (keyframe_selection_overlap, :820-837, utils/keyframe_selection.py): a
+  random sample of the frame's depth pixels is back-projected and projected into every keyframe but the last;
+  the window is a random `window - 2` of the keyframes that see any of it, plus the last keyframe and the
+  current frame.  It runs on the device (splatam_amd.keyframes.select_device, three launches, after
+  densification and before mapping) from a KeyframeBank that is appended at frame 0, at every
+  keyframe_every-th frame and at frame num_frames - 2 (:932) with the pose as estimated then; the mapper
+  gathers its per-iteration keyframes from the device-resident draws (GraphMapper.run(device_sequence=...)),
+  so frame() still reads nothing back.  Randomness comes as 32-bit words from the sequence's numpy stream
+  (`draws` records them); PerFrameSlam runs keyframes.select_literal on the same words.  The two deliberate
+  differences from the reference (the random-word mapping, distinct pixels in one 1e-4 m cell are kept) are
+  stated in splatam_amd/keyframes.py and include/gsr_glue.h.
 """
 from __future__ import annotations
 
@@ -27,6 +40,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .keyframes import KeyframeBank, WordFeed, draw_words, make_workspace, pose_w2c, select_device, \
+    select_literal, words_tensor
 from .mapper import GAUSS_KEYS, GraphMapper
 from .slam import MappingConfig, TrackingConfig, build_rotation, color_key, transform_to_frame, \
     transformed_params2depthplussilhouette
@@ -191,6 +206,18 @@ def compact_static(params: dict, alive: torch.Tensor, n_live: torch.Tensor, capa
         n_live.copy_(count)
 
 
+def _check_policy(keyframe_policy: str, window: int):
+    if keyframe_policy not in ("window", "overlap"):
+        raise ValueError(f"keyframe_policy {keyframe_policy!r}: 'window' or 'overlap'")
+    if keyframe_policy == "overlap" and window < 2:
+        raise ValueError("keyframe_policy 'overlap' needs window >= 2 (the last keyframe and the current frame)")
+
+
+def _overlap_keyframe(t: int, keyframe_every: int, num_frames: int) -> bool:
+    """scripts/splatam.py:932: frame 0, every keyframe_every-th frame and frame num_frames - 2."""
+    return t == 0 or (t + 1) % keyframe_every == 0 or t == num_frames - 2
+
+
 class SlamSequence:
     """Frames of SplaTAM's loop on a capacity-padded map with one GraphTracker and one GraphMapper.
 
@@ -202,11 +229,13 @@ class SlamSequence:
                  tracking_iters: int = 40, mapping_iters: int = 60, track_replay: int = 20, window: int = 8,
                  keyframe_every: int = 5, sil_thres: float = 0.5, track_cfg: TrackingConfig = TrackingConfig(),
                  map_cfg: MappingConfig = MappingConfig(), prune: bool | None = None, seed: int = 0,
-                 scene_radius=None):
+                 scene_radius=None, keyframe_policy: str = "window", overlap_pixels: int = 1600):
         if color_key(params) != "rgb_colors" or params["log_scales"].shape[1] != 1:
             raise ValueError("SlamSequence: SplaTAM's isotropic rgb map (the tracking fast path's form)")
         if tracking_iters % track_replay:
             raise ValueError("tracking_iters must be a multiple of track_replay")
+        _check_policy(keyframe_policy, window)
+        self.keyframe_policy, self.overlap_pixels = keyframe_policy, int(overlap_pixels)
         self.frames, self.cam, self.w2c, self.intrinsics = frames, cam, w2c, intrinsics
         self.bin_capacity = int(bin_capacity)
         self.tracking_iters, self.mapping_iters, self.window = tracking_iters, mapping_iters, window
@@ -218,8 +247,14 @@ class SlamSequence:
         self.scene_radius = scene_radius
         self.keyframes = [self._kf(0)]
         self.rng = np.random.RandomState(seed)
-        self.draws = []  # the mapper's keyframe draws per frame (window indices)
+        self.draws = []  # per frame: the mapper's keyframe draws (window indices); "overlap": the random words
         dev = params["means3D"].device
+        if keyframe_policy == "overlap":
+            f0 = frames[0]
+            self.bank = KeyframeBank(f0["im"].shape, f0["depth"].shape, dev)
+            self.feed = WordFeed(dev)
+            self.kf_workspace = make_workspace(f0["depth"].shape[-2], self.overlap_pixels, dev)
+            self.selections = []  # per frame: select_device's outputs (device tensors; nothing is read here)
         self.overflow = torch.zeros(1, dtype=torch.bool, device=dev)
         self.dstatus = torch.zeros(4, dtype=torch.int32, device=dev)
         self._build(params, int(capacity))
@@ -246,6 +281,8 @@ class SlamSequence:
         self.mapper = GraphMapper(self.params, self.keyframes, iters_per_graph=self.mapping_iters, cfg=self.map_cfg,
                                   seed=self.seed, prune=self.prune, scene_radius=self.scene_radius,
                                   alive=self.alive, capacity=self.bin_capacity)
+        if self.keyframe_policy == "overlap":
+            self.mapper.set_keyframe_bank(self.bank.im, self.bank.depth)
 
     def ensure_headroom(self, free: int) -> bool:
         """One host read of n_live: when fewer than `free` rows are left, move the map into a larger buffer
@@ -283,7 +320,10 @@ class SlamSequence:
 
     def map(self, t: int, sequence=None):
         """The mapping frame over the window (the last window - 1 keyframes + frame t), keyframe draws from the
-        sequence's numpy stream (np.random.randint, scripts/splatam.py:851) unless `sequence` is given."""
+        sequence's numpy stream (np.random.randint, scripts/splatam.py:851) unless `sequence` is given.
+        keyframe_policy "overlap": _map_overlap (`sequence`: the frame's random words)."""
+        if self.keyframe_policy == "overlap":
+            return self._map_overlap(t, sequence)
         win = self.keyframes[-(self.window - 1):] + ([self._kf(t)] if self.keyframes[-1]["id"] != t else [])
         self.mapper.set_keyframes(win)
         seq = [int(self.rng.randint(0, len(win))) for _ in range(self.mapping_iters)] if sequence is None else sequence
@@ -294,6 +334,31 @@ class SlamSequence:
         # keyframes: frame 0 and every keyframe_every-th frame (scripts/splatam.py:907-913)
         if t > 0 and (t + 1) % self.keyframe_every == 0:
             self.keyframes.append(self._kf(t))
+
+    def _map_overlap(self, t: int, words=None):
+        """The mapping frame under the overlap policy, without a host read: the frame into the bank's last
+        row, the frame's random words (overlap_pixels for the sample, one key per candidate keyframe,
+        one per mapping iteration) to the device, select_device, the mapper's replay from its draws, and the
+        keyframe bookkeeping of scripts/splatam.py:932-945."""
+        bank, f = self.bank, self.frames[t]
+        bank.set_current(f["im"], f["depth"])
+        S, n_cand = self.overlap_pixels, max(bank.n - 1, 0)
+        words = draw_words(self.rng, S + n_cand + self.mapping_iters) if words is None else \
+            np.ascontiguousarray(np.asarray(words, dtype=np.uint32))
+        if words.shape != (S + n_cand + self.mapping_iters,):
+            raise ValueError(f"frame {t}: {S + n_cand + self.mapping_iters} random words")
+        self.draws.append(words)
+        w = self.feed.push(words)
+        sel = select_device(f["depth"], self.intrinsics, pose_w2c(self.params, t), bank.est_w2c, bank.n,
+                            self.window - 2, w[:S], w[S:S + n_cand], w[S + n_cand:], bank.time, t, bank.cur_row,
+                            workspace=self.kf_workspace)
+        self.selections.append(sel)
+        self.mapper.run(check=False, device_sequence=(sel["draw_rows"], sel["draw_times"]))
+        if self.mapper.prune_at:
+            compact_static(self.params, self.alive, self.n_live, self.capacity)
+        if _overlap_keyframe(t, self.keyframe_every, len(self.frames)):
+            if bank.append(f["im"], f["depth"], self.params, t):  # (the bank doubled: new tensors)
+                self.mapper.set_keyframe_bank(bank.im, bank.depth)
 
     def frame(self, t: int, sequence=None):
         """One frame of scripts/splatam.py:697-929: tracking (t > 0), densification (t > 0), mapping."""
@@ -328,7 +393,11 @@ class PerFrameSlam:
                  mapping_iters: int = 60, track_replay: int = 20, window: int = 8, keyframe_every: int = 5,
                  sil_thres: float = 0.5, track_cfg: TrackingConfig = TrackingConfig(),
                  map_cfg: MappingConfig = MappingConfig(), prune: bool | None = None, scene_radius=None,
-                 bin_capacity: int | None = None):
+                 bin_capacity: int | None = None, keyframe_policy: str = "window", overlap_pixels: int = 1600):
+        _check_policy(keyframe_policy, window)
+        self.keyframe_policy, self.overlap_pixels = keyframe_policy, int(overlap_pixels)
+        self.kf_list = []  # "overlap": the keyframes in the order appended, each with its est_w2c snapshot
+        self.windows = []  # "overlap": per frame, the selected window's time indices
         self.p = {k: v.detach().clone() for k, v in params.items()}
         self.frames, self.cam, self.w2c, self.intrinsics = frames, cam, w2c, intrinsics
         self.tracking_iters, self.mapping_iters, self.track_replay = tracking_iters, mapping_iters, track_replay
@@ -355,12 +424,36 @@ class PerFrameSlam:
                 p["cam_trans"][..., t] = tp["cam_trans"][..., 0]
             p = add_new_gaussians_literal(p, self._kf(t), t, self.intrinsics, self.sil_thres)
         mp = {k: (v.detach().requires_grad_(True) if k in GAUSS_KEYS + ("rgb_colors",) else v) for k, v in p.items()}
-        win = self.keyframes[-(self.window - 1):] + ([self._kf(t)] if self.keyframes[-1]["id"] != t else [])
+        if self.keyframe_policy == "overlap":
+            win, sequence = self._select_overlap(p, t, sequence)
+        else:
+            win = self.keyframes[-(self.window - 1):] + ([self._kf(t)] if self.keyframes[-1]["id"] != t else [])
         m = GraphMapper(mp, win, iters_per_graph=self.mapping_iters, cfg=self.map_cfg, seed=0, prune=self.prune,
                         scene_radius=self.scene_radius, capacity=self.bin_capacity)
         m.run(sequence=sequence)
         if m.prune_at:
             mp, _, _ = m.compact()
         self.p = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in mp.items()}
-        if t > 0 and (t + 1) % self.keyframe_every == 0:
+        if self.keyframe_policy == "overlap":
+            if _overlap_keyframe(t, self.keyframe_every, len(self.frames)):
+                self.kf_list.append(dict(self._kf(t), est_w2c=pose_w2c(self.p, t)))
+        elif t > 0 and (t + 1) % self.keyframe_every == 0:
             self.keyframes.append(self._kf(t))
+
+    def _select_overlap(self, p: dict, t: int, words):
+        """keyframes.select_literal on the frame's random words (SlamSequence.draws[t]): the window's keyframe
+        dicts and the per-iteration window indices, for the per-frame GraphMapper's host path."""
+        dev = p["means3D"].device
+        S, n_kf = self.overlap_pixels, len(self.kf_list)
+        n_cand = max(n_kf - 1, 0)
+        w = words_tensor(words, dev)
+        if w.numel() != S + n_cand + self.mapping_iters:
+            raise ValueError(f"frame {t}: {S + n_cand + self.mapping_iters} random words")
+        kf_w2c = torch.stack([kf["est_w2c"].reshape(16) for kf in self.kf_list]) if n_kf else \
+            torch.zeros(0, 16, device=dev)
+        kf_time = torch.tensor([kf["id"] for kf in self.kf_list], dtype=torch.int64, device=dev)
+        sel = select_literal(self.frames[t]["depth"], self.intrinsics, pose_w2c(p, t), kf_w2c, n_kf, self.window - 2,
+                             w[:S], w[S:S + n_cand], w[S + n_cand:], kf_time, t, n_kf)
+        rows = sel["window"][:int(sel["n_window"])].tolist()
+        self.windows.append([t if r == n_kf else self.kf_list[r]["id"] for r in rows])
+        return [self._kf(t) if r == n_kf else self.kf_list[r] for r in rows], sel["draw_index"].tolist()
