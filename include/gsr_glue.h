@@ -424,6 +424,59 @@ int gsr_keyframe_select(int H, int W, const float* depth, float fx, float fy, fl
                         int* n_window, long long* draw_rows, long long* draw_times, int* sampled_pixels,
                         void* stream);
 
+/* ------------------------------------------------------------- evaluation --
+ * One frame of SplaTAM's eval() (utils/eval_helpers.py:466-512) without a host read: everything is
+ * enqueued on `stream` (one launch, six with MS-SSIM), every input but the sizes and the three
+ * scalars is read on the device when the kernels run, so the call can be captured in a graph and
+ * replayed after the four images changed in place.
+ *
+ * Inputs: im, gt_im [3,H,W] (the rendered and the captured colour); depth_sil [3,H,W] (channel 0 the
+ * rendered depth, channel 1 the silhouette); gt_depth [1,H,W].  With 0/1 float masks
+ *     valid = gt_depth > 0, presence = silhouette > sil_thres (strict),
+ *     m = valid * presence when use_sil_mask, else valid
+ * (use_sil_mask: the reference's `mapping_iters == 0 and not add_new_gaussians`), and every product
+ * below a float32 multiplication -- a NaN or inf pixel under a zero mask stays NaN, as in the reference:
+ *     wi = im * m, wg = gt_im * m;
+ *     mse_c  = sum over the H*W pixels of (wi_c - wg_c)^2, divided by H*W;
+ *     psnr   = the mean over the three channels of 20 log10(1 / sqrt(mse_c));
+ *     e      = depth * valid - gt_depth, times presence when use_sil_mask;
+ *     depth_rmse = sum(sqrt(e^2) * valid) / n_valid;  depth_l1 = sum(|e| * valid) / n_valid;
+ *     n_valid = sum(valid).
+ * depth_rmse is the reference's formula (:500-502, :507-509): the square root is taken per pixel, before
+ * the sum, so it is the same mean absolute error as depth_l1 (up to the underflow of e^2), not a root
+ * mean square; the reference writes both files (rmse.txt, l1.txt), so both columns are kept.  Nothing is
+ * special-cased: n_valid == 0 gives NaN (0 / 0) in both depth columns, mse_c == 0 gives psnr = inf.
+ * row (8 floats, device): {psnr, ms_ssim, depth_rmse, depth_l1, n_valid, mse_r, mse_g, mse_b}.
+ *
+ * ms_ssim: pytorch_msssim's ms_ssim(wi, wg, data_range=1.0, size_average=True), the call of :484,
+ * restated here from its published definition -- the package is not a dependency, and parity with it
+ * is NOT pinned by any test of this repository:
+ *   window: 11 taps, g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)) normalised to sum 1, applied separably along H
+ *     and then along W as a valid (unpadded) correlation G*: an [h,w] image gives [h - 10, w - 10].
+ *   per level and channel, X / Y the two images: mu1 = G*X, mu2 = G*Y, s1 = G*(X X) - mu1^2,
+ *     s2 = G*(Y Y) - mu2^2, s12 = G*(X Y) - mu1 mu2, C1 = 0.01^2, C2 = 0.03^2,
+ *     cs_map = (2 s12 + C2) / (s1 + s2 + C2), ssim_map = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) * cs_map;
+ *     cs, ssim = the means of the two maps over the valid output.
+ *   five levels; after each of the first four X and Y become avg_pool2d(kernel 2, stride 2, padding =
+ *     extent % 2 per axis, the zero pad counted in the divisor): an odd extent n pools the windows
+ *     [-1,0], [1,2], ..., [n-2,n-1] (index -1 a zero), each sum divided by 4, and yields (n + 1) / 2.
+ *   ms_ssim = the mean over the three channels of prod_l v_l^w_l, v_0..3 = relu(cs) of levels 0..3,
+ *     v_4 = relu(ssim) of level 4, w = [0.0448, 0.2856, 0.3001, 0.2363, 0.1333].
+ *   The definition exists for min(H, W) > 160 only: with ms_ssim != 0 a smaller image is refused
+ *   (GSR_ERR_INVALID_ARG, nothing is written); with ms_ssim == 0 the column is NaN and the pyramid is
+ *   not run.
+ * Precision: the per-pixel operations above are float32, as the reference's; the sums over the image and
+ * the window's weighted sums are accumulated in float64 in a fixed order (no float atomics: the same
+ * inputs give the same bits on every run) and rounded to float32 once, in the row; the pooled images are
+ * stored as float32.
+ * workspace: gsr_eval_workspace_bytes(H, W, ms_ssim) bytes of its own (not the reduction scratch above;
+ * 0 for sizes gsr_eval_frame refuses), 16-byte aligned, zero-filled once before its first use: its two
+ * arrival counters (in the first 16 words, whatever the sizes) return to zero and everything else is
+ * written before it is read, so one buffer of the largest size serves any sequence of sizes on one stream. */
+size_t gsr_eval_workspace_bytes(int H, int W, int ms_ssim);
+int gsr_eval_frame(int H, int W, const float* im, const float* depth_sil, const float* gt_im, const float* gt_depth,
+                   float sil_thres, int use_sil_mask, int ms_ssim, void* workspace, float* row, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

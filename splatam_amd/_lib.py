@@ -177,6 +177,10 @@ SIGNATURES = {
                                     c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                     ctypes.c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+    # include/gsr_glue.h: sequence evaluation
+    "gsr_eval_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gsr_eval_frame": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p,
+                               c_void_p, c_void_p]),
 }
 
 

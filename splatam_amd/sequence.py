@@ -375,6 +375,28 @@ class SlamSequence:
         if int(st[0]) > self.bin_capacity or int(st[1]) != 0:
             raise RuntimeError("SlamSequence: the densification render overflowed its binning capacity")
 
+    def evaluate(self, gt_w2c=None, eval_every: int = 1, ms_ssim: bool = True) -> dict:
+        """The reference's end-of-run eval() (utils/eval_helpers.py:408-640) of the padded map as it stands
+        against the capture: splatam_amd.evaluate.evaluate_sequence with the alive mask (one dual render and
+        one row of device metrics per evaluated frame, nothing read back), then the one host read of
+        evaluate.summarize.  gt_w2c ([num_frames, 4, 4] or a list): adds "ate_rmse", the estimated
+        trajectory being the first frame's w2c and the pose columns of frames 1 .. (:556-575)."""
+        from . import evaluate as ev
+        status = torch.zeros(4, dtype=torch.int32, device=self.alive.device)
+        table, times = ev.evaluate_sequence(self.params, self.frames, self.cam, self.w2c, sil_thres=self.sil_thres,
+                                            eval_every=eval_every, use_sil_mask=False, ms_ssim=ms_ssim,
+                                            alive=self.alive, bin_capacity=self.bin_capacity, status=status)
+        ate = None
+        if gt_w2c is not None:
+            est = [self.w2c] + [pose_w2c(self.params, t) for t in range(1, len(self.frames))]
+            ate = ev.ate_rmse(gt_w2c, est)
+        out = ev.summarize(table, times, ate)
+        st = status.cpu()
+        if int(st[0]) > self.bin_capacity or int(st[1]) != 0:
+            raise RuntimeError("SlamSequence.evaluate: a render overflowed its binning capacity")
+        out["table"] = table
+        return out
+
     def live_params(self) -> dict:
         """The live rows (slot order) of every per-Gaussian tensor, and the camera tensors."""
         keep = self.alive.bool()
