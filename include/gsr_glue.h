@@ -477,6 +477,53 @@ size_t gsr_eval_workspace_bytes(int H, int W, int ms_ssim);
 int gsr_eval_frame(int H, int W, const float* im, const float* depth_sil, const float* gt_im, const float* gt_depth,
                    float sil_thres, int use_sil_mask, int ms_ssim, void* workspace, float* row, void* stream);
 
+/* ---------------------------------------------------------- densification --
+ * SplaTAM's add_new_gaussians (scripts/splatam.py:384-426) on a capacity-padded map without a host
+ * read: everything is enqueued on `stream` (six launches), every input but the
+ * sizes and the scalar settings is read on the device when the kernels run, so the call can be
+ * captured in a graph and replayed after the images, the pose and n_live changed in place.  The
+ * image may have any resolution of its own (a downscaled densification frame with its intrinsics).
+ *
+ * Inputs: depth_sil [3,H,W] (the silhouette render: channel 0 the rendered depth rd, channel 1 the
+ * silhouette sil); gt_im [3,H,W]; gt_depth [1,H,W] (gt); fx, fy, cx, cy; w2c: the frame's estimated
+ * world-to-camera matrix (16 floats on the device, row-major); sil_thres; capacity.
+ * In/out: means3D [cap+1,3], rgb_colors [cap+1,3], unnorm_rotations [cap+1,4], logit_opacities
+ * [cap+1,1], log_scales [cap+1,1], alive uint8 [cap+1], n_live int64 [1], overflow (one byte, OR-ed).
+ * Out: n_added int64 [1]; dest int32 [H*W] (may be NULL): the row each pixel wrote, -1 if none.
+ * All arithmetic is float32 and every operation is rounded on its own (no contraction):
+ *   1. valid = gt > 0; err = |gt - rd| * valid (a product with 0.0 / 1.0, so a NaN or an infinite
+ *      |gt - rd| under valid == 0 is a NaN).
+ *   2. med = the value torch.median returns over all H*W values of err: element (H*W - 1) / 2 of the
+ *      ascending order (the lower median); NaN if any err is NaN.  Found by selection on err's bit
+ *      patterns (non-negative floats order as unsigned integers) in three passes of 11, 11 and 10
+ *      bits with integer histograms; nothing is sorted and no float is accumulated.
+ *   3. thr = 50 * med; selected = ((sil < sil_thres) | ((rd > gt) & (err > thr))) & valid.  Comparisons
+ *      with a NaN are false: a NaN med leaves the silhouette term alone, a NaN sil is not selected.
+ *   4. a selected pixel's row is n_live + r, r its rank among the selected pixels in row-major
+ *      order, n_live the value before the call.  Only rows in [0, capacity) are written; the sink row
+ *      `capacity` and every row no selected pixel maps to are not touched.
+ *   5. the row's values: x = (col - cx) / fx * z, y = (row - cy) / fy * z with z = gt; means3D the world
+ *      point by the closed-form rigid inverse of w2c exactly as step 2 of gsr_keyframe_select states
+ *      it (the same left-to-right sums); rgb_colors = gt_im[:, row, col]; unnorm_rotations =
+ *      (1, 0, 0, 0); logit_opacities = 0; log_scales = logf(sqrtf(q * q)), q = z / f, where f is
+ *      (fx + fy) / 2 formed in double from the two floats passed and rounded to float once; alive = 1.
+ *      (logf is the device library's: log_scales alone is not pinned bitwise.)
+ *   6. n_added = the number selected (whether or not their rows fit); n_live = min(n_live + n_added,
+ *      capacity); overflow |= (n_live + n_added > capacity).
+ * Returns GSR_ERR_INVALID_ARG and writes nothing for H or W <= 0, H * W >= 2^31, capacity < 0 or a
+ * NULL pointer other than dest.
+ * workspace: gsr_densify_workspace_bytes(H, W) bytes of its own (0 for sizes gsr_densify_frame
+ * refuses), 16-byte aligned, zero-filled once before its first use: its four arrival counters (in the
+ * first 16 words, whatever the sizes) return to zero and everything else is written before it is
+ * read (the histograms by the call's first launch), so one buffer of the largest size serves any sequence of
+ * sizes on one stream. */
+size_t gsr_densify_workspace_bytes(int H, int W);
+int gsr_densify_frame(int H, int W, const float* depth_sil, const float* gt_im, const float* gt_depth, float fx,
+                      float fy, float cx, float cy, const float* w2c, float sil_thres, int capacity, float* means3D,
+                      float* rgb_colors, float* unnorm_rotations, float* logit_opacities, float* log_scales,
+                      unsigned char* alive, long long* n_live, unsigned char* overflow, long long* n_added, int* dest,
+                      void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

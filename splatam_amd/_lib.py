@@ -181,6 +181,11 @@ SIGNATURES = {
     "gsr_eval_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gsr_eval_frame": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p,
                                c_void_p, c_void_p]),
+    # include/gsr_glue.h: densification
+    "gsr_densify_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gsr_densify_frame": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
+                                  c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

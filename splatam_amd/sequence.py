@@ -19,6 +19,13 @@ raises (check()) when the capacity is exhausted.  The tracker renders
 from a one-column pose slot and slot targets that each frame fills; the mapper draws from a keyframe window
 set per frame (GraphMapper.set_keyframes).
 
+Densification has two forms (`densify_mode`): "torch" (the default), densify_static as above, and "device",
+the silhouette render followed by splatam_amd.densify.densify_device (gsr_densify_frame: the median by
+selection, the ranks and the new rows in six launches; only selected pixels write).  With densify_frames /
+densify_cam / densify_intrinsics either form renders and reads a densification frame of its own resolution
+(the reference's densification_image_height / width, scripts/splatam.py:801-812); tracking, mapping and the
+keyframe bank keep the full-resolution frames.
+
 Two keyframe policies (`keyframe_policy`):
 * "window" (the default): the last `window - 1` keyframes plus the current frame; frame 0 and every
   keyframe_every-th frame are keyframes.  The draws are window indices from the sequence's numpy stream.
@@ -40,6 +47,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .densify import ROW_KEYS, check_densify_args, densify_device
+from .densify import make_workspace as make_densify_workspace
 from .keyframes import KeyframeBank, WordFeed, draw_words, make_workspace, pose_w2c, select_device, \
     select_literal, words_tensor
 from .mapper import GAUSS_KEYS, GraphMapper
@@ -165,6 +174,27 @@ def add_new_gaussians_literal(params: dict, curr: dict, t: int, intrinsics, sil_
     return out
 
 
+def add_new_gaussians_device(params: dict, curr: dict, t: int, intrinsics, sil_thres: float = 0.5) -> dict:
+    """add_new_gaussians on an unpadded map through the kernel of the padded one: the unpadded silhouette
+    render, gsr_densify_frame (splatam_amd.densify.densify_device) on a throw-away padded copy with room
+    for every pixel, and the rows up to n_live sliced out with one host read -- what torch.cat would hold,
+    so the per-frame loop stays the bitwise comparison form of SlamSequence(densify_mode="device")."""
+    ds = render_depth_sil(params, curr, t)
+    H, W = ds.shape[-2], ds.shape[-1]
+    capacity = params["means3D"].shape[0] + H * W
+    dev = ds.device
+    with torch.no_grad():
+        padded, alive, n_live = pad_map({k: params[k] for k in ROW_KEYS}, capacity)
+        overflow = torch.zeros(1, dtype=torch.bool, device=dev)
+        densify_device(padded, alive, n_live, overflow, curr, pose_w2c(params, t), intrinsics, sil_thres, capacity,
+                       ds.contiguous(), make_densify_workspace(H, W, dev))
+        n = int(n_live.item())
+    out = dict(params)
+    for k in ROW_KEYS:
+        out[k] = padded[k][:n].clone().requires_grad_(params[k].requires_grad)
+    return out
+
+
 def densify_static(params: dict, alive: torch.Tensor, n_live: torch.Tensor, overflow: torch.Tensor, curr: dict,
                    t: int, intrinsics, sil_thres: float, capacity: int, bin_capacity: int, status):
     """add_new_gaussians on a capacity-padded map, without a host synchronisation: the selected pixels'
@@ -229,12 +259,16 @@ class SlamSequence:
                  tracking_iters: int = 40, mapping_iters: int = 60, track_replay: int = 20, window: int = 8,
                  keyframe_every: int = 5, sil_thres: float = 0.5, track_cfg: TrackingConfig = TrackingConfig(),
                  map_cfg: MappingConfig = MappingConfig(), prune: bool | None = None, seed: int = 0,
-                 scene_radius=None, keyframe_policy: str = "window", overlap_pixels: int = 1600):
+                 scene_radius=None, keyframe_policy: str = "window", overlap_pixels: int = 1600,
+                 densify_mode: str = "torch", densify_frames=None, densify_cam=None, densify_intrinsics=None):
         if color_key(params) != "rgb_colors" or params["log_scales"].shape[1] != 1:
             raise ValueError("SlamSequence: SplaTAM's isotropic rgb map (the tracking fast path's form)")
         if tracking_iters % track_replay:
             raise ValueError("tracking_iters must be a multiple of track_replay")
         _check_policy(keyframe_policy, window)
+        check_densify_args(densify_mode, densify_frames, densify_cam, densify_intrinsics, frames)
+        self.densify_mode, self.densify_frames = densify_mode, densify_frames
+        self.densify_cam, self.densify_intrinsics = densify_cam, densify_intrinsics
         self.keyframe_policy, self.overlap_pixels = keyframe_policy, int(overlap_pixels)
         self.frames, self.cam, self.w2c, self.intrinsics = frames, cam, w2c, intrinsics
         self.bin_capacity = int(bin_capacity)
@@ -257,6 +291,9 @@ class SlamSequence:
             self.selections = []  # per frame: select_device's outputs (device tensors; nothing is read here)
         self.overflow = torch.zeros(1, dtype=torch.bool, device=dev)
         self.dstatus = torch.zeros(4, dtype=torch.int32, device=dev)
+        if densify_mode == "device":
+            d0 = (densify_frames if densify_frames is not None else frames)[0]["depth"]
+            self.densify_workspace = make_densify_workspace(d0.shape[-2], d0.shape[-1], dev)
         self._build(params, int(capacity))
 
     def _build(self, params: dict, capacity: int):
@@ -314,9 +351,26 @@ class SlamSequence:
             p["cam_unnorm_rots"][..., t] = self.slot["cam_unnorm_rots"][..., 0]
             p["cam_trans"][..., t] = self.slot["cam_trans"][..., 0]
 
+    def _densify_kf(self, t: int) -> tuple[dict, tuple]:
+        """The frame densification reads and its intrinsics: the tracking frame, or the densification
+        resolution's (densify_frames / densify_cam / densify_intrinsics, scripts/splatam.py:801-812)."""
+        if self.densify_frames is None:
+            return self._kf(t), self.intrinsics
+        f = self.densify_frames[t]
+        return {"cam": self.densify_cam, "w2c": self.w2c, "im": f["im"], "depth": f["depth"], "id": t}, \
+            self.densify_intrinsics
+
     def densify(self, t: int):
-        densify_static(self.params, self.alive, self.n_live, self.overflow, self._kf(t), t, self.intrinsics,
-                       self.sil_thres, self.capacity, self.bin_capacity, self.dstatus)
+        """add_new_gaussians without a host read.  densify_mode "torch": densify_static; "device": the
+        silhouette render, then splatam_amd.densify.densify_device (one call, only the new rows written)."""
+        kf, intr = self._densify_kf(t)
+        if self.densify_mode == "torch":
+            densify_static(self.params, self.alive, self.n_live, self.overflow, kf, t, intr,
+                           self.sil_thres, self.capacity, self.bin_capacity, self.dstatus)
+            return
+        ds = render_depth_sil(self.params, kf, t, self.alive, self.bin_capacity, self.dstatus)
+        densify_device(self.params, self.alive, self.n_live, self.overflow, kf, pose_w2c(self.params, t), intr,
+                       self.sil_thres, self.capacity, ds, self.densify_workspace)
 
     def map(self, t: int, sequence=None):
         """The mapping frame over the window (the last window - 1 keyframes + frame t), keyframe draws from the
@@ -415,8 +469,12 @@ class PerFrameSlam:
                  mapping_iters: int = 60, track_replay: int = 20, window: int = 8, keyframe_every: int = 5,
                  sil_thres: float = 0.5, track_cfg: TrackingConfig = TrackingConfig(),
                  map_cfg: MappingConfig = MappingConfig(), prune: bool | None = None, scene_radius=None,
-                 bin_capacity: int | None = None, keyframe_policy: str = "window", overlap_pixels: int = 1600):
+                 bin_capacity: int | None = None, keyframe_policy: str = "window", overlap_pixels: int = 1600,
+                 densify_mode: str = "torch", densify_frames=None, densify_cam=None, densify_intrinsics=None):
         _check_policy(keyframe_policy, window)
+        check_densify_args(densify_mode, densify_frames, densify_cam, densify_intrinsics, frames)
+        self.densify_mode, self.densify_frames = densify_mode, densify_frames
+        self.densify_cam, self.densify_intrinsics = densify_cam, densify_intrinsics
         self.keyframe_policy, self.overlap_pixels = keyframe_policy, int(overlap_pixels)
         self.kf_list = []  # "overlap": the keyframes in the order appended, each with its est_w2c snapshot
         self.windows = []  # "overlap": per frame, the selected window's time indices
@@ -444,7 +502,12 @@ class PerFrameSlam:
             with torch.no_grad():
                 p["cam_unnorm_rots"][..., t] = tp["cam_unnorm_rots"][..., 0]
                 p["cam_trans"][..., t] = tp["cam_trans"][..., 0]
-            p = add_new_gaussians_literal(p, self._kf(t), t, self.intrinsics, self.sil_thres)
+            kf, intr = self._kf(t), self.intrinsics
+            if self.densify_frames is not None:
+                f = self.densify_frames[t]
+                kf, intr = dict(kf, cam=self.densify_cam, im=f["im"], depth=f["depth"]), self.densify_intrinsics
+            add = add_new_gaussians_device if self.densify_mode == "device" else add_new_gaussians_literal
+            p = add(p, kf, t, intr, self.sil_thres)
         mp = {k: (v.detach().requires_grad_(True) if k in GAUSS_KEYS + ("rgb_colors",) else v) for k, v in p.items()}
         if self.keyframe_policy == "overlap":
             win, sequence = self._select_overlap(p, t, sequence)
