@@ -889,6 +889,12 @@ __device__ __forceinline__ float ld_agent(const float* p) {
 __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+__device__ __forceinline__ void st_agent(double* p, double v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ double ld_agent(const double* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 // The last workgroup's fixed-order gather of per-workgroup partials: thread t adds values
 // k < N of part[stride * b + k] for b = t, t + nt, t + 2 nt, ... in that order -- the same
 // sums, bit for bit, as the plain loop (v starts at +0, and the out-of-range slots add +0),
@@ -1428,6 +1434,9 @@ hipError_t launch_sh_bwd(const Camera& cam, const GaussIn& g, GeomPtrs geo, cons
 // error reporting shared by the C entry points (gsr_last_error)
 int fail(int code, const std::string& msg);
 int hip_fail(hipError_t e, const char* where);
+// the sequence steps' argument tests: an image whose pixel index fits an int, a workspace's alignment
+inline bool image_size_ok(int H, int W) { return H > 0 && W > 0 && (long long)H * W <= 0x7fffffffLL; }
+inline bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
 // backward_power != 1 (the vendored renderCUDAFused semantics, backward.cu:850-1140)
 // backward_power == 2 through per-instance second moments (gsr_backward.hip, gauss_bwd_mom_kernel)
 int moments_record_floats(bool sh);

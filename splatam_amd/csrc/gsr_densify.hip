@@ -30,13 +30,13 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_glue.h"
-#include "gsr_common.h"
+#include "gsr_seq_common.h"
 
 namespace gsr {
 namespace {
 
-constexpr int DN_BLOCK = 256;
-constexpr int DN_WAVES = DN_BLOCK / 64;
+constexpr int DN_BLOCK = SEQ_BLOCK;
+constexpr int DN_WAVES = SEQ_WAVES;
 constexpr int DN_ITEMS = 8;                       // pixels per thread
 constexpr int DN_TILE = DN_BLOCK * DN_ITEMS;      // pixels per workgroup
 constexpr int DN_CHUNKS = DN_TILE / 64;           // ballot words per workgroup
@@ -138,16 +138,8 @@ dn_select_kernel(int pass, int N, const float* __restrict__ depth_sil, const flo
         c[j] = ld_agent(hist + tid * (DN_BINS / DN_BLOCK) + j);
         sum += c[j];
     }
-    s_scan[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < DN_BLOCK; d <<= 1) {  // inclusive Hillis-Steele over the 256 chunk sums
-        const uint32_t add = tid >= d ? s_scan[tid - d] : 0u;
-        __syncthreads();
-        s_scan[tid] += add;
-        __syncthreads();
-    }
+    uint32_t below = block_scan_incl(sum, s_scan) - sum;
     if (pass == 0 && tid == DN_BLOCK - 1) ws[DN_NAN] = c[DN_BINS / DN_BLOCK - 1];  // bin 2047: the NaN keys
-    uint32_t below = s_scan[tid] - sum;
     if (want >= below && want < below + sum) {  // (one thread: the bins' total exceeds the rank)
         int j = 0;
 #pragma unroll
@@ -197,35 +189,12 @@ dn_count_kernel(int N, const float* __restrict__ depth_sil, const float* __restr
         if (lane == 0) mask[i * DN_WAVES + wave] = m;
         count += (uint32_t)__popcll(m);
     }
-    if (lane == 0) s_wave[wave] = count;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t total = 0;
-        for (int w = 0; w < DN_WAVES; w++) total += s_wave[w];
-        st_agent(cnt + blockIdx.x, total);
-    }
+    block_count_publish(count, s_wave, cnt + blockIdx.x);
     if (!last_block_arrive(ws + 3)) return;
-    // ---- last workgroup: exclusive scan of the workgroups' counts (thread t owns [t * per, (t + 1) * per))
-    const int nb = lay.nb;
-    const int per = (nb + DN_BLOCK - 1) / DN_BLOCK;
-    const int b0 = min(nb, tid * per), b1 = min(nb, b0 + per);
-    uint32_t sum = 0;
-    for (int b = b0; b < b1; b++) sum += ld_agent(cnt + b);
-    s_scan[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < DN_BLOCK; d <<= 1) {
-        const uint32_t add = tid >= d ? s_scan[tid - d] : 0u;
-        __syncthreads();
-        s_scan[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = s_scan[tid] - sum;
-    for (int b = b0; b < b1; b++) {
-        excl[b] = run;
-        run += ld_agent(cnt + b);
-    }
+    // ---- last workgroup: the exclusive scan of the workgroups' counts
+    const uint32_t total_added = last_block_scan_excl(cnt, lay.nb, excl, s_scan);
     if (tid == DN_BLOCK - 1) {
-        const long long added = (long long)s_scan[tid];
+        const long long added = (long long)total_added;
         const long long old = n_live[0];  // (read before the new value is written)
         *(long long*)(ws + DN_BASE) = old;
         const long long total = old + added;
@@ -261,13 +230,7 @@ dn_scatter_kernel(int H, int W, const float* __restrict__ gt_im, const float* __
     __syncthreads();
     const long long base = *(const long long*)(ws + DN_BASE) + (long long)ws[lay.excl + blockIdx.x];
     const size_t p0 = (size_t)blockIdx.x * DN_TILE;
-    // the rigid inverse [R^T, -R^T t] of w2c, every sum left to right (gsr_keyframe_select, step 2)
-    float r[3][3], t[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        r[a][0] = w2c[a]; r[a][1] = w2c[4 + a]; r[a][2] = w2c[8 + a];
-        t[a] = -(r[a][0] * w2c[3] + r[a][1] * w2c[7] + r[a][2] * w2c[11]);
-    }
+    const RigidInverse c2w = rigid_inverse(w2c);
 #pragma unroll
     for (int i = 0; i < DN_ITEMS; i++) {
         const size_t p = p0 + (size_t)i * DN_BLOCK + tid;
@@ -283,14 +246,11 @@ dn_scatter_kernel(int H, int W, const float* __restrict__ gt_im, const float* __
         if (row < 0) continue;
         const int py = (int)(p / (size_t)W), px = (int)(p - (size_t)py * W);
         const float z = gt_depth[p];
-        const float x = ((float)px - cam.cx) / cam.fx * z;
-        const float y = ((float)py - cam.cy) / cam.fy * z;
+        const float3 w = backproject(px, py, z, cam.fx, cam.fy, cam.cx, cam.cy, c2w);
         const size_t o = (size_t)row;
+        means3D[3 * o + 0] = w.x; means3D[3 * o + 1] = w.y; means3D[3 * o + 2] = w.z;
 #pragma unroll
-        for (int a = 0; a < 3; a++) {
-            means3D[3 * o + a] = r[a][0] * x + r[a][1] * y + r[a][2] * z + t[a];
-            rgb[3 * o + a] = gt_im[(size_t)a * N + p];
-        }
+        for (int a = 0; a < 3; a++) rgb[3 * o + a] = gt_im[(size_t)a * N + p];
         rot[4 * o + 0] = 1.f; rot[4 * o + 1] = 0.f; rot[4 * o + 2] = 0.f; rot[4 * o + 3] = 0.f;
         logit_opac[o] = 0.f;
         const float q = z / cam.f;
@@ -307,7 +267,7 @@ using namespace gsr;
 extern "C" {
 
 size_t gsr_densify_workspace_bytes(int H, int W) {
-    if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) return 0;
+    if (!image_size_ok(H, W)) return 0;
     return DnLayout::make((long long)H * W).total;
 }
 
@@ -316,13 +276,12 @@ int gsr_densify_frame(int H, int W, const float* depth_sil, const float* gt_im, 
                       float* rgb_colors, float* unnorm_rotations, float* logit_opacities, float* log_scales,
                       unsigned char* alive, long long* n_live, unsigned char* overflow, long long* n_added, int* dest,
                       void* workspace, void* stream) {
-    if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL)
-        return fail(GSR_ERR_INVALID_ARG, "densify_frame: bad image size");
+    if (!image_size_ok(H, W)) return fail(GSR_ERR_INVALID_ARG, "densify_frame: bad image size");
     if (capacity < 0) return fail(GSR_ERR_INVALID_ARG, "densify_frame: negative capacity");
     if (!depth_sil || !gt_im || !gt_depth || !w2c || !means3D || !rgb_colors || !unnorm_rotations ||
         !logit_opacities || !log_scales || !alive || !n_live || !overflow || !n_added || !workspace)
         return fail(GSR_ERR_INVALID_ARG, "densify_frame: null pointer");
-    if ((uintptr_t)workspace % 16) return fail(GSR_ERR_INVALID_ARG, "densify_frame: workspace must be 16-byte aligned");
+    if (!aligned16(workspace)) return fail(GSR_ERR_INVALID_ARG, "densify_frame: workspace must be 16-byte aligned");
     const int N = H * W;
     const DnLayout lay = DnLayout::make(N);
     uint32_t* const ws = (uint32_t*)workspace;

@@ -73,13 +73,6 @@ struct EvLayout {
     }
 };
 
-__device__ __forceinline__ void st_agent(double* p, double v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double ld_agent(const double* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Sums v over the workgroup in a fixed order (each wave's lane tree, then the four waves); every thread
 // returns with the sums in v.  s_red: EV_WAVES * N doubles, free again after the call.
 template <int N>
@@ -310,19 +303,19 @@ using namespace gsr;
 extern "C" {
 
 size_t gsr_eval_workspace_bytes(int H, int W, int ms_ssim) {
-    if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) return 0;
+    if (!image_size_ok(H, W)) return 0;
     if (ms_ssim && (H < EV_MIN_SIDE || W < EV_MIN_SIDE)) return 0;
     return EvLayout::make(H, W, ms_ssim != 0).total;
 }
 
 int gsr_eval_frame(int H, int W, const float* im, const float* depth_sil, const float* gt_im, const float* gt_depth,
                    float sil_thres, int use_sil_mask, int ms_ssim, void* workspace, float* row, void* stream) {
-    if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) return fail(GSR_ERR_INVALID_ARG, "eval_frame: bad image size");
+    if (!image_size_ok(H, W)) return fail(GSR_ERR_INVALID_ARG, "eval_frame: bad image size");
     if (ms_ssim && (H < EV_MIN_SIDE || W < EV_MIN_SIDE))
         return fail(GSR_ERR_INVALID_ARG, "eval_frame: MS-SSIM is defined for min(H, W) > 160 only (ms_ssim = 0 skips it)");
     if (!im || !depth_sil || !gt_im || !gt_depth || !workspace || !row)
         return fail(GSR_ERR_INVALID_ARG, "eval_frame: null pointer");
-    if ((uintptr_t)workspace % 16) return fail(GSR_ERR_INVALID_ARG, "eval_frame: workspace must be 16-byte aligned");
+    if (!aligned16(workspace)) return fail(GSR_ERR_INVALID_ARG, "eval_frame: workspace must be 16-byte aligned");
     const EvLayout lay = EvLayout::make(H, W, ms_ssim != 0);
     char* const ws = (char*)workspace;
     uint32_t* const counters = (uint32_t*)ws;

@@ -22,13 +22,13 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_glue.h"
-#include "gsr_common.h"
+#include "gsr_seq_common.h"
 
 namespace gsr {
 namespace {
 
-constexpr int KF_BLOCK = 256;
-constexpr int KF_WAVES = KF_BLOCK / 64;
+constexpr int KF_BLOCK = SEQ_BLOCK;
+constexpr int KF_WAVES = SEQ_WAVES;
 constexpr int KF_MAX_ROWS = 4096;     // the row scan's LDS prefix
 constexpr int KF_MAX_WINDOW = 1024;   // k_select + 2 (the window's LDS copy)
 // workspace words: [0] kf_rows_kernel's arrival counter, [1] kf_select_kernel's (both zero between
@@ -70,35 +70,13 @@ kf_rows_kernel(int H, int W, const float* __restrict__ depth, uint32_t* __restri
         const bool v = c < W && depth[(size_t)row * W + c] > 0.f;
         cnt += (uint32_t)__popcll(__ballot(v));
     }
-    if ((tid & 63) == 0) s_wave[tid >> 6] = cnt;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t total = 0;
-        for (int w = 0; w < KF_WAVES; w++) total += s_wave[w];
-        st_agent(rowcnt + row, total);
-    }
+    block_count_publish(cnt, s_wave, rowcnt + row);
     if (!last_block_arrive(ws + 0)) return;
-    // last workgroup: exclusive scan of the H row counts (thread t owns rows [t * per, (t + 1) * per))
-    const int per = (H + KF_BLOCK - 1) / KF_BLOCK;
-    const int r0 = tid * per, r1 = min(H, r0 + per);
-    uint32_t sum = 0;
-    for (int r = r0; r < r1; r++) sum += ld_agent(rowcnt + r);
-    s_scan[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < KF_BLOCK; d <<= 1) {  // inclusive Hillis-Steele over the 256 chunk sums
-        const uint32_t add = tid >= d ? s_scan[tid - d] : 0u;
-        __syncthreads();
-        s_scan[tid] += add;
-        __syncthreads();
-    }
-    uint32_t run = s_scan[tid] - sum;
-    for (int r = r0; r < r1; r++) {
-        rowpre[r] = run;
-        run += ld_agent(rowcnt + r);
-    }
+    // last workgroup: the exclusive scan of the H row counts
+    const uint32_t total = last_block_scan_excl(rowcnt, H, rowpre, s_scan);
     if (tid == KF_BLOCK - 1) {
-        rowpre[H] = s_scan[tid];
-        ws[KF_NVALID] = s_scan[tid];
+        rowpre[H] = total;
+        ws[KF_NVALID] = total;
     }
 }
 
@@ -144,20 +122,11 @@ kf_sample_kernel(int H, int W, const float* __restrict__ depth, KfCam cam, const
         }
         if (col >= 0 && col < W) {
             pix = lo * W + col;
-            const float z = depth[pix];
-            const float x = ((float)col - cam.cx) / cam.fx * z;
-            const float y = ((float)lo - cam.cy) / cam.fy * z;
-            // the rigid inverse [R^T, -R^T t] of the current w2c, every sum left to right
-            float w[3];
-#pragma unroll
-            for (int a = 0; a < 3; a++) {
-                const float ra = w2c[a], rb = w2c[4 + a], rc = w2c[8 + a];
-                const float ta = -(ra * w2c[3] + rb * w2c[7] + rc * w2c[11]);
-                w[a] = ra * x + rb * y + rc * z + ta;
-            }
-            const bool origin = rintf(w[0] * 10000.f) == 0.f && rintf(w[1] * 10000.f) == 0.f &&
-                                rintf(w[2] * 10000.f) == 0.f;
-            out = make_float4(w[0], w[1], w[2], (!drawn_twice && !origin) ? 1.f : 0.f);
+            const float3 w = backproject(col, lo, depth[pix], cam.fx, cam.fy, cam.cx, cam.cy,
+                                          rigid_inverse(w2c));
+            const bool origin = rintf(w.x * 10000.f) == 0.f && rintf(w.y * 10000.f) == 0.f &&
+                                rintf(w.z * 10000.f) == 0.f;
+            out = make_float4(w.x, w.y, w.z, (!drawn_twice && !origin) ? 1.f : 0.f);
         }
     }
     if (lane == 0) {
@@ -274,7 +243,7 @@ int gsr_keyframe_select(int H, int W, const float* depth, float fx, float fy, fl
                         long long time_idx, int cur_row, void* workspace, int* overlap, int* n_points, int* window,
                         int* n_window, long long* draw_rows, long long* draw_times, int* sampled_pixels,
                         void* stream) {
-    if (H <= 0 || W <= 0 || H > KF_MAX_ROWS || (long long)H * W > 0x7fffffffLL)
+    if (!image_size_ok(H, W) || H > KF_MAX_ROWS)
         return fail(GSR_ERR_INVALID_ARG, "keyframe_select: bad image size (at most 4096 rows)");
     if (n_kf < 0 || k_select < 0 || k_select + 2 > KF_MAX_WINDOW || S < 0 || n_draws < 0 || cur_row < n_kf)
         return fail(GSR_ERR_INVALID_ARG, "keyframe_select: bad sizes (k_select <= 1022, cur_row >= n_kf)");
@@ -282,7 +251,7 @@ int gsr_keyframe_select(int H, int W, const float* depth, float fx, float fy, fl
         (n_kf > 0 && (!kf_w2c || !kf_time)) || (n_kf > 1 && (!perm_key || !overlap)) ||
         (n_draws > 0 && (!u_draw || !draw_rows || !draw_times)))
         return fail(GSR_ERR_INVALID_ARG, "keyframe_select: null pointer");
-    if ((uintptr_t)workspace % 16) return fail(GSR_ERR_INVALID_ARG, "keyframe_select: workspace must be 16-byte aligned");
+    if (!aligned16(workspace)) return fail(GSR_ERR_INVALID_ARG, "keyframe_select: workspace must be 16-byte aligned");
     const KfLayout lay = KfLayout::make(H, S);
     uint32_t* const ws = (uint32_t*)workspace;
     float4* const pts = (float4*)(ws + lay.pts);

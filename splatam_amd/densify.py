@@ -25,6 +25,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from ._devcall import backproject_literal, check_rc, f32, require, zero_workspace
+
 ROW_KEYS = ("means3D", "rgb_colors", "unnorm_rotations", "logit_opacities", "log_scales")
 
 
@@ -35,7 +37,7 @@ def workspace_bytes(H: int, W: int) -> int:
 
 def make_workspace(H: int, W: int, device) -> torch.Tensor:
     """A zero-filled workspace for densify_device (any smaller image can share it)."""
-    return torch.zeros((workspace_bytes(H, W) + 3) // 4, dtype=torch.int32, device=device)
+    return zero_workspace(workspace_bytes(H, W), device)
 
 
 def mean_focal(fx: float, fy: float) -> np.float32:
@@ -63,9 +65,7 @@ def densify_device(params: dict, alive: torch.Tensor, n_live: torch.Tensor, over
               ("alive", alive, torch.uint8, capacity + 1), ("n_live", n_live, torch.int64, 1)]
     if dest is not None:
         checks.append(("dest", dest, torch.int32, H * W))
-    for name, t, dt, n in checks:
-        if t.dtype != dt or t.device != dev or not t.is_contiguous() or t.numel() < n:
-            raise RuntimeError(f"densify_device: {name} must be a contiguous {dt} tensor of >= {n} elements on {dev}")
+    require("densify_device", dev, checks)
     if overflow.device != dev or overflow.element_size() != 1 or overflow.numel() < 1:
         raise RuntimeError("densify_device: overflow must be a one-byte tensor on the map's device")
     if im.shape[-2:] != depth_sil.shape[-2:] or depth.shape[-2:] != depth_sil.shape[-2:]:
@@ -79,8 +79,7 @@ def densify_device(params: dict, alive: torch.Tensor, n_live: torch.Tensor, over
                                alive.data_ptr(), n_live.data_ptr(), overflow.data_ptr(), n_added.data_ptr(),
                                None if dest is None else dest.data_ptr(), workspace.data_ptr(),
                                torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"gsr_densify_frame: {lib.gsr_last_error().decode(errors='replace')}")
+    check_rc(rc, "gsr_densify_frame")
     return n_added
 
 
@@ -94,26 +93,18 @@ def densify_literal(curr: dict, w2c: torch.Tensor, intrinsics, sil_thres: float,
     im, gt = curr["im"], curr["depth"][0]
     H, W = int(gt.shape[-2]), int(gt.shape[-1])
     dev = gt.device
-    f32 = lambda v: torch.tensor(float(v), dtype=torch.float32, device=dev)  # noqa: E731
-    fx, fy, cx, cy = (f32(v) for v in intrinsics)
-    f = f32(mean_focal(intrinsics[0], intrinsics[1]))
+    fx, fy, cx, cy = (f32(v, dev) for v in intrinsics)
+    f = f32(mean_focal(intrinsics[0], intrinsics[1]), dev)
     with torch.no_grad():
         rd, sil = depth_sil[0], depth_sil[1]
         valid = gt > 0
         err = torch.abs(gt - rd) * valid.to(torch.float32)
         med = err.reshape(-1).median()  # the lower median; NaN if any err is NaN
-        thr = f32(50.0) * med
-        mask = ((sil < f32(sil_thres)) | ((rd > gt) & (err > thr))) & valid
+        thr = f32(50.0, dev) * med
+        mask = ((sil < f32(sil_thres, dev)) | ((rd > gt) & (err > thr))) & valid
         rowi, coli = torch.nonzero(mask, as_tuple=True)  # row-major order (host synchronisation)
         z = gt[rowi, coli]
-        x = (coli.to(torch.float32) - cx) / fx * z
-        y = (rowi.to(torch.float32) - cy) / fy * z
-        m = w2c.reshape(-1).to(torch.float32)
-        pw = []
-        for a in range(3):  # the rigid inverse [R^T, -R^T t], every sum left to right
-            ra, rb, rc = m[a], m[4 + a], m[8 + a]
-            ta = -(ra * m[3] + rb * m[7] + rc * m[11])
-            pw.append(ra * x + rb * y + rc * z + ta)
+        pw = backproject_literal(coli, rowi, z, fx, fy, cx, cy, w2c)
         q = z / f
         n = int(z.numel())
         rot = torch.zeros(n, 4, dtype=torch.float32, device=dev)

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from ._devcall import check_rc, require, zero_workspace
 from .keyframes import pose_w2c
 from .slam import transform_to_frame, transformed_params2depthplussilhouette, transformed_params2rendervar
 
@@ -50,7 +51,7 @@ def make_workspace(H: int, W: int, device, ms_ssim: bool = True) -> torch.Tensor
     if n == 0:
         raise RuntimeError(f"make_workspace: {H}x{W} with ms_ssim={bool(ms_ssim)} is not a size gsr_eval_frame takes "
                            f"(MS-SSIM needs min(H, W) > {MS_SSIM_MIN_SIDE})")
-    return torch.zeros((n + 3) // 4, dtype=torch.int32, device=device)
+    return zero_workspace(n, device)
 
 
 def frame_metrics(im: torch.Tensor, depth_sil: torch.Tensor, gt_im: torch.Tensor, gt_depth: torch.Tensor,
@@ -66,11 +67,11 @@ def frame_metrics(im: torch.Tensor, depth_sil: torch.Tensor, gt_im: torch.Tensor
         raise RuntimeError("frame_metrics: im must be [3, H, W]")
     H, W = int(im.shape[1]), int(im.shape[2])
     dev = im.device
-    for name, t, n in (("im", im, 3 * H * W), ("depth_sil", depth_sil, 3 * H * W), ("gt_im", gt_im, 3 * H * W),
-                       ("gt_depth", gt_depth, H * W), ("row", row, 8)):
-        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or \
-                (t.numel() != n if name != "row" else t.numel() < n):
-            raise RuntimeError(f"frame_metrics: {name} must be a contiguous float32 tensor of {n} elements on {dev}")
+    f32 = torch.float32
+    require("frame_metrics", dev, (("im", im, f32, 3 * H * W), ("depth_sil", depth_sil, f32, 3 * H * W),
+                                   ("gt_im", gt_im, f32, 3 * H * W), ("gt_depth", gt_depth, f32, H * W),
+                                   ("row", row, f32, 8)),
+            exact=("im", "depth_sil", "gt_im", "gt_depth"), size="float32 tensor of {n}")
     need = workspace_bytes(H, W, ms_ssim)  # (0: a size the library refuses; its message is the error)
     if workspace.device != dev or not workspace.is_contiguous() or \
             workspace.numel() * workspace.element_size() < need:
@@ -78,8 +79,7 @@ def frame_metrics(im: torch.Tensor, depth_sil: torch.Tensor, gt_im: torch.Tensor
     rc = lib.gsr_eval_frame(H, W, im.data_ptr(), depth_sil.data_ptr(), gt_im.data_ptr(), gt_depth.data_ptr(),
                             float(sil_thres), int(bool(use_sil_mask)), int(bool(ms_ssim)), workspace.data_ptr(),
                             row.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc < 0:
-        raise RuntimeError(f"gsr_eval_frame: {lib.gsr_last_error().decode(errors='replace')}")
+    check_rc(rc, "gsr_eval_frame")
     return row
 
 

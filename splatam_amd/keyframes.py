@@ -28,6 +28,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from ._devcall import backproject_literal, check_rc, f32, require, zero_workspace
 from .slam import build_rotation
 
 EDGE = 20  # keyframe_selection_overlap's image border
@@ -150,7 +151,7 @@ def workspace_bytes(H: int, S: int) -> int:
 
 def make_workspace(H: int, S: int, device) -> torch.Tensor:
     """A zero-filled workspace for select_device (any smaller H / S can share it)."""
-    return torch.zeros((workspace_bytes(H, S) + 3) // 4, dtype=torch.int32, device=device)
+    return zero_workspace(workspace_bytes(H, S), device)
 
 
 def select_device(depth: torch.Tensor, intrinsics, w2c: torch.Tensor, kf_w2c: torch.Tensor, n_kf: int, k_select: int,
@@ -168,12 +169,11 @@ def select_device(depth: torch.Tensor, intrinsics, w2c: torch.Tensor, kf_w2c: to
     H, W = int(depth.shape[-2]), int(depth.shape[-1])
     dev = depth.device
     n_kf, k_select, S, n_draws = int(n_kf), int(k_select), int(u_pix.numel()), int(u_draw.numel())
-    for name, t, dt, n in (("depth", depth, torch.float32, H * W), ("w2c", w2c, torch.float32, 16),
-                           ("kf_w2c", kf_w2c, torch.float32, 16 * n_kf), ("kf_time", kf_time, torch.int64, n_kf),
-                           ("u_pix", u_pix, torch.int32, S), ("perm_key", perm_key, torch.int32, max(n_kf - 1, 0)),
-                           ("u_draw", u_draw, torch.int32, n_draws)):
-        if t.dtype != dt or t.device != dev or not t.is_contiguous() or t.numel() < n:
-            raise RuntimeError(f"select_device: {name} must be a contiguous {dt} tensor of >= {n} elements on {dev}")
+    require("select_device", dev, (("depth", depth, torch.float32, H * W), ("w2c", w2c, torch.float32, 16),
+                                   ("kf_w2c", kf_w2c, torch.float32, 16 * n_kf), ("kf_time", kf_time, torch.int64, n_kf),
+                                   ("u_pix", u_pix, torch.int32, S),
+                                   ("perm_key", perm_key, torch.int32, max(n_kf - 1, 0)),
+                                   ("u_draw", u_draw, torch.int32, n_draws)))
     if workspace is None:
         workspace = make_workspace(H, S, dev)
     if workspace.device != dev or workspace.numel() * workspace.element_size() < workspace_bytes(H, S):
@@ -189,8 +189,7 @@ def select_device(depth: torch.Tensor, intrinsics, w2c: torch.Tensor, kf_w2c: to
                                  out["n_window"].data_ptr(), out["draw_rows"].data_ptr(),
                                  out["draw_times"].data_ptr(), None if px is None else px.data_ptr(),
                                  torch.cuda.current_stream(dev).cuda_stream)
-    if rc < 0:
-        raise RuntimeError(f"gsr_keyframe_select: {lib.gsr_last_error().decode(errors='replace')}")
+    check_rc(rc, "gsr_keyframe_select")
     return out
 
 
@@ -204,8 +203,7 @@ def select_literal(depth: torch.Tensor, intrinsics, w2c: torch.Tensor, kf_w2c: t
     dev = depth.device
     n_kf, k_select, S, n_draws = int(n_kf), int(k_select), int(u_pix.numel()), int(u_draw.numel())
     n_cand = max(n_kf - 1, 0)
-    f32 = lambda v: torch.tensor(float(v), dtype=torch.float32, device=dev)  # noqa: E731
-    fx, fy, cx, cy = (f32(v) for v in intrinsics)
+    fx, fy, cx, cy = (f32(v, dev) for v in intrinsics)
     with torch.no_grad():
         flat = depth.reshape(-1)
         valid = torch.nonzero(flat > 0)[:, 0]  # row-major, torch.where's order (host synchronisation)
@@ -218,15 +216,7 @@ def select_literal(depth: torch.Tensor, intrinsics, w2c: torch.Tensor, kf_w2c: t
             r = (_u64(u_pix) * n_valid) >> 32
             pix = valid[r]
             row, col = torch.div(pix, W, rounding_mode="floor"), pix % W
-            z = flat[pix]
-            x = (col.to(torch.float32) - cx) / fx * z
-            y = (row.to(torch.float32) - cy) / fy * z
-            m = w2c.reshape(-1).to(torch.float32)
-            pw = []
-            for a in range(3):  # the rigid inverse [R^T, -R^T t], every sum left to right
-                ra, rb, rc = m[a], m[4 + a], m[8 + a]
-                ta = -(ra * m[3] + rb * m[7] + rc * m[11])
-                pw.append(ra * x + rb * y + rc * z + ta)
+            pw = backproject_literal(col, row, flat[pix], fx, fy, cx, cy, w2c)
             twice = (r[:, None] == r[None, :]).sum(dim=1) > 1
             origin = (torch.round(pw[0] * 1e4) == 0) & (torch.round(pw[1] * 1e4) == 0) & \
                 (torch.round(pw[2] * 1e4) == 0)
@@ -238,7 +228,7 @@ def select_literal(depth: torch.Tensor, intrinsics, w2c: torch.Tensor, kf_w2c: t
             px = c(0) * wx + c(1) * wy + c(2) * wz + c(3)
             py = c(4) * wx + c(5) * wy + c(6) * wz + c(7)
             pz = c(8) * wx + c(9) * wy + c(10) * wz + c(11)
-            zz = pz + f32(1e-5)
+            zz = pz + f32(1e-5, dev)
             u = (fx * px + cx * pz) / zz
             v = (fy * py + cy * pz) / zz
             inside = (u > EDGE) & (u < W - EDGE) & (v > EDGE) & (v < H - EDGE) & (zz > 0) & keep[None, :]

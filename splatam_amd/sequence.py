@@ -243,12 +243,58 @@ def _check_policy(keyframe_policy: str, window: int):
         raise ValueError("keyframe_policy 'overlap' needs window >= 2 (the last keyframe and the current frame)")
 
 
-def _overlap_keyframe(t: int, keyframe_every: int, num_frames: int) -> bool:
-    """scripts/splatam.py:932: frame 0, every keyframe_every-th frame and frame num_frames - 2."""
-    return t == 0 or (t + 1) % keyframe_every == 0 or t == num_frames - 2
+class _SequenceBase:
+    """What SlamSequence and PerFrameSlam share: the loop's options, the keyframe dicts, the densification frame,
+    the "window" policy's window, both policies' keyframe rule and an "overlap" frame's random-word counts."""
+
+    OPTIONS = ("frames", "cam", "w2c", "intrinsics", "bin_capacity", "tracking_iters", "mapping_iters", "track_replay",
+               "window", "keyframe_every", "sil_thres", "track_cfg", "map_cfg", "prune", "scene_radius",
+               "keyframe_policy", "overlap_pixels", "densify_mode", "densify_frames", "densify_cam",
+               "densify_intrinsics")
+
+    def _set_options(self, args: dict):
+        """Stores the constructor arguments both classes take (OPTIONS, out of the constructor's locals()) as
+        attributes of their names, validated, and starts the keyframe list with frame 0."""
+        for k in self.OPTIONS:
+            setattr(self, k, args[k])
+        _check_policy(self.keyframe_policy, self.window)
+        check_densify_args(self.densify_mode, self.densify_frames, self.densify_cam, self.densify_intrinsics,
+                           self.frames)
+        self.overlap_pixels = int(self.overlap_pixels)
+        if self.scene_radius is None:  # initialize_first_timestep: max depth / scene_radius_depth_ratio (3, the config's)
+            self.scene_radius = self.frames[0]["depth"].max() / 3.0
+        self.keyframes = [self._kf(0)]
+
+    def _kf(self, t: int) -> dict:
+        return {"cam": self.cam, "w2c": self.w2c, "im": self.frames[t]["im"], "depth": self.frames[t]["depth"], "id": t}
+
+    def _densify_kf(self, t: int) -> tuple[dict, tuple]:
+        """The frame densification reads and its intrinsics: the tracking frame, or the densification
+        resolution's (densify_frames / densify_cam / densify_intrinsics, scripts/splatam.py:801-812)."""
+        if self.densify_frames is None:
+            return self._kf(t), self.intrinsics
+        f = self.densify_frames[t]
+        return dict(self._kf(t), cam=self.densify_cam, im=f["im"], depth=f["depth"]), self.densify_intrinsics
+
+    def _window(self, t: int) -> list:  # "window": the last window - 1 keyframes plus frame t
+        return self.keyframes[-(self.window - 1):] + ([self._kf(t)] if self.keyframes[-1]["id"] != t else [])
+
+    def _is_keyframe(self, t: int) -> bool:
+        """Whether frame t joins the keyframes after its mapping: every keyframe_every-th frame
+        (scripts/splatam.py:907-913; frame 0 is one from the start) and, "overlap" (:932), frames 0 and num_frames - 2."""
+        every = (t + 1) % self.keyframe_every == 0
+        if self.keyframe_policy == "overlap":
+            return every or t in (0, len(self.frames) - 2)
+        return every and t > 0
+
+    def _word_counts(self, n_kf: int) -> tuple[int, int, int]:
+        """An "overlap" frame's random words with n_kf keyframes: the sample's, the candidate keyframes' keys, and
+        all of them (with one per mapping iteration)."""
+        S, n_cand = self.overlap_pixels, max(n_kf - 1, 0)
+        return S, n_cand, S + n_cand + self.mapping_iters
 
 
-class SlamSequence:
+class SlamSequence(_SequenceBase):
     """Frames of SplaTAM's loop on a capacity-padded map with one GraphTracker and one GraphMapper.
 
     params: the initial map (SplaTAM's init from frame 0; isotropic, rgb colours) with one pose column per frame;
@@ -265,21 +311,8 @@ class SlamSequence:
             raise ValueError("SlamSequence: SplaTAM's isotropic rgb map (the tracking fast path's form)")
         if tracking_iters % track_replay:
             raise ValueError("tracking_iters must be a multiple of track_replay")
-        _check_policy(keyframe_policy, window)
-        check_densify_args(densify_mode, densify_frames, densify_cam, densify_intrinsics, frames)
-        self.densify_mode, self.densify_frames = densify_mode, densify_frames
-        self.densify_cam, self.densify_intrinsics = densify_cam, densify_intrinsics
-        self.keyframe_policy, self.overlap_pixels = keyframe_policy, int(overlap_pixels)
-        self.frames, self.cam, self.w2c, self.intrinsics = frames, cam, w2c, intrinsics
-        self.bin_capacity = int(bin_capacity)
-        self.tracking_iters, self.mapping_iters, self.window = tracking_iters, mapping_iters, window
-        self.keyframe_every, self.sil_thres = keyframe_every, sil_thres
-        self.track_replay, self.track_cfg, self.map_cfg, self.prune, self.seed = \
-            track_replay, track_cfg, map_cfg, prune, seed
-        if scene_radius is None:  # initialize_first_timestep: max depth / scene_radius_depth_ratio (3, the config's)
-            scene_radius = frames[0]["depth"].max() / 3.0
-        self.scene_radius = scene_radius
-        self.keyframes = [self._kf(0)]
+        self._set_options(locals())
+        self.bin_capacity, self.seed = int(bin_capacity), seed
         self.rng = np.random.RandomState(seed)
         self.draws = []  # per frame: the mapper's keyframe draws (window indices); "overlap": the random words
         dev = params["means3D"].device
@@ -333,9 +366,6 @@ class SlamSequence:
         self._build(self.live_params(), max(2 * self.capacity, n + int(free)))
         return True
 
-    def _kf(self, t: int) -> dict:
-        return {"cam": self.cam, "w2c": self.w2c, "im": self.frames[t]["im"], "depth": self.frames[t]["depth"], "id": t}
-
     def track(self, t: int):
         """initialize_camera_pose, then tracking_iters iterations from the pose slot (best candidate written
         back into column t)."""
@@ -350,15 +380,6 @@ class SlamSequence:
         with torch.no_grad():
             p["cam_unnorm_rots"][..., t] = self.slot["cam_unnorm_rots"][..., 0]
             p["cam_trans"][..., t] = self.slot["cam_trans"][..., 0]
-
-    def _densify_kf(self, t: int) -> tuple[dict, tuple]:
-        """The frame densification reads and its intrinsics: the tracking frame, or the densification
-        resolution's (densify_frames / densify_cam / densify_intrinsics, scripts/splatam.py:801-812)."""
-        if self.densify_frames is None:
-            return self._kf(t), self.intrinsics
-        f = self.densify_frames[t]
-        return {"cam": self.densify_cam, "w2c": self.w2c, "im": f["im"], "depth": f["depth"], "id": t}, \
-            self.densify_intrinsics
 
     def densify(self, t: int):
         """add_new_gaussians without a host read.  densify_mode "torch": densify_static; "device": the
@@ -378,16 +399,18 @@ class SlamSequence:
         keyframe_policy "overlap": _map_overlap (`sequence`: the frame's random words)."""
         if self.keyframe_policy == "overlap":
             return self._map_overlap(t, sequence)
-        win = self.keyframes[-(self.window - 1):] + ([self._kf(t)] if self.keyframes[-1]["id"] != t else [])
+        win = self._window(t)
         self.mapper.set_keyframes(win)
         seq = [int(self.rng.randint(0, len(win))) for _ in range(self.mapping_iters)] if sequence is None else sequence
         self.draws.append(seq)
         self.mapper.run(check=False, sequence=seq)
+        self._compact_pruned()
+        if self._is_keyframe(t):
+            self.keyframes.append(self._kf(t))
+
+    def _compact_pruned(self):
         if self.mapper.prune_at:  # the frame's pruned Gaussians removed for good (in place, no sync)
             compact_static(self.params, self.alive, self.n_live, self.capacity)
-        # keyframes: frame 0 and every keyframe_every-th frame (scripts/splatam.py:907-913)
-        if t > 0 and (t + 1) % self.keyframe_every == 0:
-            self.keyframes.append(self._kf(t))
 
     def _map_overlap(self, t: int, words=None):
         """The mapping frame under the overlap policy, without a host read: the frame into the bank's last
@@ -396,11 +419,11 @@ class SlamSequence:
         keyframe bookkeeping of scripts/splatam.py:932-945."""
         bank, f = self.bank, self.frames[t]
         bank.set_current(f["im"], f["depth"])
-        S, n_cand = self.overlap_pixels, max(bank.n - 1, 0)
-        words = draw_words(self.rng, S + n_cand + self.mapping_iters) if words is None else \
+        S, n_cand, total = self._word_counts(bank.n)
+        words = draw_words(self.rng, total) if words is None else \
             np.ascontiguousarray(np.asarray(words, dtype=np.uint32))
-        if words.shape != (S + n_cand + self.mapping_iters,):
-            raise ValueError(f"frame {t}: {S + n_cand + self.mapping_iters} random words")
+        if words.shape != (total,):
+            raise ValueError(f"frame {t}: {total} random words")
         self.draws.append(words)
         w = self.feed.push(words)
         sel = select_device(f["depth"], self.intrinsics, pose_w2c(self.params, t), bank.est_w2c, bank.n,
@@ -408,9 +431,8 @@ class SlamSequence:
                             workspace=self.kf_workspace)
         self.selections.append(sel)
         self.mapper.run(check=False, device_sequence=(sel["draw_rows"], sel["draw_times"]))
-        if self.mapper.prune_at:
-            compact_static(self.params, self.alive, self.n_live, self.capacity)
-        if _overlap_keyframe(t, self.keyframe_every, len(self.frames)):
+        self._compact_pruned()
+        if self._is_keyframe(t):
             if bank.append(f["im"], f["depth"], self.params, t):  # (the bank doubled: new tensors)
                 self.mapper.set_keyframe_bank(bank.im, bank.depth)
 
@@ -458,7 +480,7 @@ class SlamSequence:
                 for k, v in self.params.items()}
 
 
-class PerFrameSlam:
+class PerFrameSlam(_SequenceBase):
     """The same frames in the form a shape-changing map forces on captured graphs: per frame a fresh
     GraphTracker on the frame's pose (probe, warm-up, capture), add_new_gaussians by torch.cat, a fresh
     GraphMapper on the grown map (probe, warm-up, capture) and, after its pruning, compact().  The comparison
@@ -471,23 +493,10 @@ class PerFrameSlam:
                  map_cfg: MappingConfig = MappingConfig(), prune: bool | None = None, scene_radius=None,
                  bin_capacity: int | None = None, keyframe_policy: str = "window", overlap_pixels: int = 1600,
                  densify_mode: str = "torch", densify_frames=None, densify_cam=None, densify_intrinsics=None):
-        _check_policy(keyframe_policy, window)
-        check_densify_args(densify_mode, densify_frames, densify_cam, densify_intrinsics, frames)
-        self.densify_mode, self.densify_frames = densify_mode, densify_frames
-        self.densify_cam, self.densify_intrinsics = densify_cam, densify_intrinsics
-        self.keyframe_policy, self.overlap_pixels = keyframe_policy, int(overlap_pixels)
+        self._set_options(locals())
         self.kf_list = []  # "overlap": the keyframes in the order appended, each with its est_w2c snapshot
         self.windows = []  # "overlap": per frame, the selected window's time indices
         self.p = {k: v.detach().clone() for k, v in params.items()}
-        self.frames, self.cam, self.w2c, self.intrinsics = frames, cam, w2c, intrinsics
-        self.tracking_iters, self.mapping_iters, self.track_replay = tracking_iters, mapping_iters, track_replay
-        self.window, self.keyframe_every, self.sil_thres = window, keyframe_every, sil_thres
-        self.track_cfg, self.map_cfg, self.prune, self.bin_capacity = track_cfg, map_cfg, prune, bin_capacity
-        self.scene_radius = frames[0]["depth"].max() / 3.0 if scene_radius is None else scene_radius
-        self.keyframes = [self._kf(0)]
-
-    def _kf(self, t: int) -> dict:
-        return {"cam": self.cam, "w2c": self.w2c, "im": self.frames[t]["im"], "depth": self.frames[t]["depth"], "id": t}
 
     def frame(self, t: int, sequence):
         p = self.p
@@ -502,38 +511,35 @@ class PerFrameSlam:
             with torch.no_grad():
                 p["cam_unnorm_rots"][..., t] = tp["cam_unnorm_rots"][..., 0]
                 p["cam_trans"][..., t] = tp["cam_trans"][..., 0]
-            kf, intr = self._kf(t), self.intrinsics
-            if self.densify_frames is not None:
-                f = self.densify_frames[t]
-                kf, intr = dict(kf, cam=self.densify_cam, im=f["im"], depth=f["depth"]), self.densify_intrinsics
+            kf, intr = self._densify_kf(t)
             add = add_new_gaussians_device if self.densify_mode == "device" else add_new_gaussians_literal
             p = add(p, kf, t, intr, self.sil_thres)
         mp = {k: (v.detach().requires_grad_(True) if k in GAUSS_KEYS + ("rgb_colors",) else v) for k, v in p.items()}
         if self.keyframe_policy == "overlap":
             win, sequence = self._select_overlap(p, t, sequence)
         else:
-            win = self.keyframes[-(self.window - 1):] + ([self._kf(t)] if self.keyframes[-1]["id"] != t else [])
+            win = self._window(t)
         m = GraphMapper(mp, win, iters_per_graph=self.mapping_iters, cfg=self.map_cfg, seed=0, prune=self.prune,
                         scene_radius=self.scene_radius, capacity=self.bin_capacity)
         m.run(sequence=sequence)
         if m.prune_at:
             mp, _, _ = m.compact()
         self.p = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in mp.items()}
-        if self.keyframe_policy == "overlap":
-            if _overlap_keyframe(t, self.keyframe_every, len(self.frames)):
+        if self._is_keyframe(t):
+            if self.keyframe_policy == "overlap":
                 self.kf_list.append(dict(self._kf(t), est_w2c=pose_w2c(self.p, t)))
-        elif t > 0 and (t + 1) % self.keyframe_every == 0:
-            self.keyframes.append(self._kf(t))
+            else:
+                self.keyframes.append(self._kf(t))
 
     def _select_overlap(self, p: dict, t: int, words):
         """keyframes.select_literal on the frame's random words (SlamSequence.draws[t]): the window's keyframe
         dicts and the per-iteration window indices, for the per-frame GraphMapper's host path."""
         dev = p["means3D"].device
-        S, n_kf = self.overlap_pixels, len(self.kf_list)
-        n_cand = max(n_kf - 1, 0)
+        n_kf = len(self.kf_list)
         w = words_tensor(words, dev)
-        if w.numel() != S + n_cand + self.mapping_iters:
-            raise ValueError(f"frame {t}: {S + n_cand + self.mapping_iters} random words")
+        S, n_cand, total = self._word_counts(n_kf)
+        if w.numel() != total:
+            raise ValueError(f"frame {t}: {total} random words")
         kf_w2c = torch.stack([kf["est_w2c"].reshape(16) for kf in self.kf_list]) if n_kf else \
             torch.zeros(0, 16, device=dev)
         kf_time = torch.tensor([kf["id"] for kf in self.kf_list], dtype=torch.int64, device=dev)

@@ -132,6 +132,22 @@ def test_full_frame_and_todays_mask(cuda, refs):
     assert torch.equal(today, call.dest >= 0) and int(today.sum()) == ref["count"] > 1000
 
 
+def test_count_scan_with_two_workgroups_per_thread(cuda, refs):
+    """3 x 174763 = 524289 pixels, 257 workgroups of 2048: the last workgroup's scan gives threads 0 .. 127 two
+    workgroups each, thread 128 one (the last, a single pixel's) and threads 129 .. 255 none.  No smaller image
+    reaches that branch.  (Its restatement stays out of `refs`' table: the log_scales bound is the existing one.)"""
+    H, W = 3, 174763
+    case = dr.make_case(H, W, "random", seed=1)
+    ref = dr.restate(case)
+    sel = np.flatnonzero(ref["mask"].reshape(-1))
+    assert 0 < ref["count"] == len(sel) < H * W and ((sel // 2048) % 2 == 1).any()  # an odd workgroup's prefix is read
+    call = Call(case, n_live=37, capacity=37 + H * W + 5, overflow=0, dev=cuda)
+    ws = call.run()
+    print(f"{H}x{W} random: {ref['count']} selected, med {ref['med']!r}")
+    check(call, ref, refs[1])
+    _word_count_zero(ws)
+
+
 @pytest.mark.parametrize("content", ["random", "quantised", "zeros90", "denormal", "nan_depth", "all_selected"])
 def test_selection_equals_todays_mask(cuda, refs, content):
     from splatam_amd.sequence import non_presence_mask

@@ -39,6 +39,21 @@ def test_kernel_matches_restatement(cuda, W, H, S, n_kf):
     kr.check(out, ref)
 
 
+@pytest.mark.parametrize("W,H", [(64, 300), (64, 600)])
+def test_row_scan_with_several_rows_per_thread(cuda, W, H):
+    """More than 256 rows: the last workgroup's scan gives a thread two rows (H = 300, threads 150 .. 255 none)
+    or three (H = 600, threads 200 .. 255 none).  The seed was picked with the restatement alone, so that the
+    window is not trivial: a wrong row prefix moves the sampled pixels, and with them every other output."""
+    c = kr.make_case(W, H, 65, 9, seed=1, zero_rows=ZERO_ROWS)
+    ref = kr.restate(c)
+    assert ref["n_points"] > 0 and (ref["sure"] > 0).any() and ref["borderline"].max() == 0
+    out = kfm.select_device(*kr.to_torch(c, cuda), pixels=True)
+    torch.cuda.synchronize()
+    print(f"{W}x{H}: n_points {int(out['n_points'])}, eligible {ref['n_eligible']}, overlap {out['overlap'].tolist()}")
+    kr.check(out, ref)
+    assert torch.equal(out["overlap"].cpu().to(torch.int64), torch.from_numpy(ref["sure"]))  # (no borderline sample)
+
+
 @pytest.mark.parametrize("W,H,S,n_kf", [(100, 75, 65, 9), (320, 240, 1600, 300)])
 def test_kernel_equals_literal_bits(cuda, W, H, S, n_kf):
     """select_literal's elementwise float32 ops (here on CPU tensors) and the kernels form the same bits: every
