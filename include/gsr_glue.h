@@ -380,6 +380,34 @@ int gsr_points_to_camera(int P, const float* means, const float* w2c, float* pts
 int gsr_fisher_accumulate(int P, const float* dmeans3D, const float* dopacity, const float* weight, float* H,
                           void* stream);
 
+/* The silhouette half of the fork's mixed view gain (scripts/ros_handler.py:251-359, send_gains:
+ * g_sil = (sil < 0.5).sum() / (W H) of a second, depth/silhouette render per candidate pose,
+ * get_renders :955-985) without that render: *count (device, one unsigned) = the number of pixels
+ * inside the image whose silhouette is < sil_thres (strict), from the buffers a finished forward
+ * left -- geom_buffer, binning_buffer, image_buffer and num_rendered as gsr_backward takes them,
+ * after gsr_forward and after gsr_forward_static (num_rendered = the capacity it returned) alike;
+ * P, the image size and bg as in that forward's call (of `settings` only image_width,
+ * image_height and bg are read; bg on the device, when the kernel runs).
+ *   The silhouette of a pixel is the forward's image of a colour channel whose per-Gaussian value
+ * is 1 with background bg[1] (SplaTAM's [z, 1, z^2] render, channel 1), decision by decision: the
+ * tile's sorted, block-masked list walked front to back, alpha = min(0.99, opacity * exp2(p2)),
+ * pairs with p2 > 0 or alpha < 1/255 skipped, the walk ended at T (1 - alpha) < 1e-4, C += alpha T
+ * (product and sum each rounded), the value C + T bg[1].  The count therefore equals the count
+ * taken from that render.  With bg[1] >= 0 a pixel's walk ends as soon as C >= sil_thres (the
+ * value cannot fall below it again); with bg[1] < 0 it ends where the forward's does.
+ *   The entry point zeroes *count itself (a one-thread kernel with a plain store, ahead of the count
+ * kernel on `stream`; no memset node), then one 256-thread workgroup per tile adds its pixels with
+ * one integer atomic: the result does not depend on the arrival order.  Everything is enqueued on
+ * `stream` and nothing waits on the host, so the call can be captured in a graph.  After a
+ * static-capacity forward that overflowed (num_rendered > capacity or a tile list longer than the
+ * per-tile sort handles) the lists are not valid: the kernel does not walk them and *count is
+ * unspecified (it stays zero); the forward's status row reports the overflow.  P == 0: every
+ * silhouette is 0 (the forward writes zero images), *count = W H if 0 < sil_thres else 0, and the
+ * buffers are not read.  Returns GSR_OK or a negative error code (gsr_last_error names the call). */
+int gsr_silhouette_count(const gsr_settings* settings, int P, int num_rendered, const void* geom_buffer,
+                         const void* binning_buffer, const void* image_buffer, float sil_thres, unsigned* count,
+                         void* stream);
+
 /* ------------------------------------------------------- keyframe selection --
  * SplaTAM's overlap keyframe selection (utils/keyframe_selection.py, scripts/splatam.py:820-837)
  * without a host read: everything is enqueued on `stream` (three launches), every input but the

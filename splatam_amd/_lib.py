@@ -171,6 +171,8 @@ SIGNATURES = {
     # include/gsr_glue.h: Fisher scoring glue
     "gsr_points_to_camera": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_fisher_accumulate": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_silhouette_count": (c_int, [ctypes.POINTER(GsrSettings), c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
+                                     c_void_p, c_void_p]),
     # include/gsr_glue.h: overlap keyframe selection
     "gsr_keyframe_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gsr_keyframe_select": (c_int, [c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p,

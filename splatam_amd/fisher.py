@@ -27,8 +27,16 @@ capacity forwards (gsr_forward_static), power-2 backwards and the per-pose reduc
 (H accumulation for the visited poses, or the EIG score of each candidate) are captured
 once into a HIP graph and replayed with the poses written into a device [K,4,4] tensor.
 Every pose's Hessian is bitwise the per-pose FisherScorer.hessian's.
+
+The node publishes a mixed gain per candidate (send_gains, :251-359): the EIG next to a silhouette
+gain, the share of pixels whose rendered silhouette is below 0.5, which the reference takes from a
+second render per pose (get_renders, :955-985) and reads back.  silhouette_count() and
+BatchedFisher(mode="gains") take it from the buffers the scoring forward leaves anyway
+(gsr_silhouette_count, csrc/gsr_viewgain.hip), so each pose is binned once and nothing is read back.
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 import torch.distributed as dist
@@ -59,6 +67,78 @@ def camera_points(means: torch.Tensor, w2c: torch.Tensor) -> torch.Tensor:
     if rc != 0:
         raise RuntimeError(f"gsr_points_to_camera: {lib.gsr_last_error().decode(errors='replace')}")
     return pts
+
+
+def _count_into(cam, P: int, n: int, geom, binning, img, sil_thres: float, out: torch.Tensor):
+    """gsr_silhouette_count on a finished forward's buffers into out (device int32 [1]; the C side writes an
+    unsigned, W H < 2^31 here)."""
+    from . import _C
+    from ._lib import lib
+    dev = out.device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    st, keep = _C._settings(cam.bg, cam.viewmatrix, cam.projmatrix, cam.campos, cam.tanfovx, cam.tanfovy,
+                            cam.image_height, cam.image_width, cam.scale_modifier, cam.sh_degree, cam.prefiltered,
+                            dev, stream)
+    ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None  # noqa: E731
+    rc = lib.gsr_silhouette_count(ctypes.byref(st), int(P), int(n), ptr(geom), ptr(binning), ptr(img),
+                                  float(sil_thres), out.data_ptr(), stream)
+    del keep
+    if rc != 0:
+        raise RuntimeError(f"gsr_silhouette_count: {lib.gsr_last_error().decode(errors='replace')}")
+
+
+def silhouette_count(scorer: "FisherScorer", w2c: torch.Tensor, sil_thres: float = 0.5) -> torch.Tensor:
+    """(sil < sil_thres).sum() of send_gains (ros_handler.py:296-299) for one camera (w2c [4,4]): the number of
+    pixels whose silhouette -- channel 1 of the [z, 1, z^2] render of the map moved into the candidate frame --
+    is below the threshold, as a device int32 scalar (no read-back).  camera_points, the ordinary forward,
+    then gsr_silhouette_count on that forward's buffers: no second render.
+
+    The map is moved as compute_Hessian moves it (means only).  The reference's silhouette render
+    (transform_gaussians, :905-952) also rotates the quaternions; for SplaTAM's isotropic map the two see the
+    same geometry, for an anisotropic one they do not (BatchedFisher mode "gains" refuses such a map)."""
+    from . import _C
+    if scorer._hessian_fn is not None:
+        raise RuntimeError("silhouette_count renders through the rasterizer (no hessian_fn override)")
+    cam = scorer.cam
+    means = scorer.params["means3D"].detach()
+    with torch.no_grad():
+        pts = camera_points(means, w2c)
+        out = torch.empty(1, dtype=torch.int32, device=means.device)
+        e = torch.Tensor([])
+        P = pts.shape[0]
+        if P == 0:  # the forward of an empty map runs nothing and leaves no buffers
+            _count_into(cam, 0, 0, None, None, None, sil_thres, out)
+            return out[0]
+        n, _, _, geom, binning, img, _ = _C.rasterize_gaussians(
+            cam.bg, pts, scorer.colors.detach(), scorer.opacities.detach(), scorer.scales.detach(),
+            scorer.rotations.detach(), cam.scale_modifier, e, cam.viewmatrix, cam.projmatrix, cam.tanfovx,
+            cam.tanfovy, cam.image_height, cam.image_width, e, cam.sh_degree, cam.campos, cam.prefiltered)
+        _count_into(cam, P, n, geom, binning, img, sil_thres, out)
+    return out[0]
+
+
+def _nl(g: torch.Tensor) -> torch.Tensor:
+    return 3400.0 / (1.0 + torch.exp(-0.002 * g)) - 1700.0  # ros_handler.py:316,318
+
+
+def combine_gains(counts: torch.Tensor, eig: torch.Tensor, n_pixels: int, k_sil: float = 1.0, k_eig: float = 1.0,
+                  k_sum: float = 1.0, nl_sil: bool = False, nl_eig: bool = False) -> torch.Tensor:
+    """send_gains' mixed gain (ros_handler.py:299-322) for n poses, in float64 on the inputs' device:
+    counts [n] pixels below the silhouette threshold, eig [n] compute_eig_score.  Returns [n,3]
+    (g_sil, g_eig, gain): g_sil = count / (W H) * k_sil, g_eig = eig * k_eig (0 when k_eig == 0, which
+    skips the score there), each optionally through 3400 / (1 + exp(-0.002 g)) - 1700,
+    gain = k_sum * (g_eig + g_sil)."""
+    # (a tensor divisor: torch divides a device tensor by a Python scalar as a product with its reciprocal,
+    # one rounding more than the reference's float division)
+    g_sil = counts.double() / torch.full_like(counts, float(n_pixels), dtype=torch.float64)
+    g_eig = eig.double() if k_eig != 0 else torch.zeros_like(eig, dtype=torch.float64)
+    g_sil = g_sil * float(k_sil)
+    g_eig = g_eig * float(k_eig)
+    if nl_sil:
+        g_sil = _nl(g_sil)
+    if nl_eig:
+        g_eig = _nl(g_eig)
+    return torch.stack([g_sil, g_eig, float(k_sum) * (g_eig + g_sil)], dim=1)
 
 
 class FisherScorer:
@@ -149,24 +229,72 @@ class FisherScorer:
             out[idx] = gathered[rr][:len(idx)]
         return out
 
+    def view_gains(self, w2cs, batch: "BatchedFisher | None" = None, sil_thres: float = 0.5, **weights) -> torch.Tensor:
+        """send_gains' (g_sil, g_eig, gain) for every candidate pose: float64 [n,3] in pose order on every rank,
+        sharded and gathered like eig_scores.  weights: k_sil, k_eig, k_sum, nl_sil, nl_eig (combine_gains).
+        batch: a BatchedFisher(mode="gains") -- K candidate poses per graph launch (its sil_thres holds);
+        without one each pose is hessian() + silhouette_count()."""
+        if self.H_train_inv is None:
+            raise RuntimeError("fit_visited() first (H_train_inv)")
+        r, w = sd.world()
+        n = len(w2cs)
+        per = -(-n // w) if n else 0
+        dev = self.H_train_inv.device
+        npix = self.cam.image_width * self.cam.image_height
+        local = torch.zeros(max(per, 1), 3, dtype=torch.float64, device=dev)
+        mine = list(range(r, n, w))
+
+        def eager(idx):
+            eig = torch.stack([(self.hessian(w2cs[j]) * self.H_train_inv).sum().double() for j in idx])
+            cnt = torch.stack([silhouette_count(self, w2cs[j], sil_thres) for j in idx])
+            return combine_gains(cnt, eig, npix, **weights)
+
+        step = batch.K if batch is not None else 1
+        for c in range(0, len(mine), step):
+            idx = mine[c:c + step]
+            g = batch.gains([w2cs[j] for j in idx], self.H_train_inv, **weights) if batch is not None else None
+            if g is None:  # no batch, or a capacity overflow in the graph: this chunk on the eager path
+                g = eager(idx)
+            local[c:c + len(idx)] = g
+        if w == 1:
+            return local[:n]
+        gathered = [torch.zeros_like(local) for _ in range(w)]
+        dist.all_gather(gathered, local)
+        out = torch.zeros(n, 3, dtype=torch.float64, device=dev)
+        for rr in range(w):
+            idx = list(range(rr, n, w))
+            out[idx] = gathered[rr][:len(idx)]
+        return out
+
 
 class BatchedFisher:
     """K poses of FisherScorer's Hessian per HIP-graph launch.
 
     mode "sum": `hessian_sum(w2cs)` returns sum_k H(w2c_k) (compute_H_visited_inv's H_train before the
     all-reduce); mode "scores": `scores(w2cs, H_inv)` returns [sum(H(w2c_k) * H_inv) for k] (float64 like
-    FisherScorer.eig_scores).  Fewer than K poses pad the batch with weight-0 slots.  The binning capacity
+    FisherScorer.eig_scores); mode "gains": `gains(w2cs, H_inv, ...)` returns send_gains' (g_sil, g_eig, gain)
+    per pose -- per slot the transform, the static forward, gsr_silhouette_count on that forward's buffers, the
+    power-2 backward and "scores"' reduction, so each pose is binned once; g_eig / k_eig is bitwise "scores"'
+    result.  Gains mode takes SplaTAM's isotropic map only (log_scales [P,1]): the reference renders the
+    silhouette with the quaternions rotated into the candidate frame (transform_gaussians, ros_handler.py:905-952)
+    and the Hessian without (compute_Hessian), which is the same geometry only for isotropic Gaussians -- one
+    forward then serves both; an anisotropic map raises ValueError.
+    Fewer than K poses pad the batch with weight-0 slots.  The binning capacity
     comes from eager probes of `probe_w2cs` times `headroom`; `overflowed()` reports (sticky) whether a
     replay exceeded it (results then invalid: rebuild with more headroom)."""
 
     def __init__(self, scorer: FisherScorer, K: int, mode: str = "sum", probe_w2cs=None, headroom: float = 1.5,
-                 min_extra: int = 65536):
-        from . import _C
+                 min_extra: int = 65536, sil_thres: float = 0.5):
         if scorer._hessian_fn is not None:
             raise RuntimeError("BatchedFisher renders through the rasterizer (no hessian_fn override)")
-        if mode not in ("sum", "scores"):
-            raise ValueError("mode is 'sum' or 'scores'")
+        if mode not in ("sum", "scores", "gains"):
+            raise ValueError("mode is 'sum', 'scores' or 'gains'")
+        if mode == "gains" and scorer.params["log_scales"].shape[-1] != 1:
+            raise ValueError("mode 'gains' takes an isotropic map only (log_scales [P,1]): the reference's "
+                             "silhouette render rotates the Gaussians, its Hessian render does not")
+        from . import _C
         self.sc, self.K, self.mode = scorer, int(K), mode
+        self.sil_thres = float(sil_thres)
         cam = scorer.cam
         means = scorer.params["means3D"].detach().contiguous()
         dev = means.device
@@ -176,6 +304,7 @@ class BatchedFisher:
         self.weight = torch.zeros(self.K, device=dev)
         self.H_inv = torch.zeros(P, 4, device=dev)
         self.status = torch.zeros(self.K, 4, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(self.K, dtype=torch.int32, device=dev) if mode == "gains" else None
         self.seed = torch.full((3, cam.image_height, cam.image_width), SEED, device=dev)  # ros_handler.py:888
         self.e = torch.Tensor([])
         probes = list(probe_w2cs) if probe_w2cs is not None else [torch.eye(4, device=dev)]
@@ -210,6 +339,8 @@ class BatchedFisher:
         self._k = k
         pts = camera_points(self.means, self.w2c[k])
         n, color, radii, geom, binning, img, depth = self._forward(_C, pts, self.capacity)
+        if self.mode == "gains":  # the silhouette count on this forward's lists, ahead of the backward
+            _count_into(cam, pts.shape[0], n, geom, binning, img, self.sil_thres, self.counts[k:k + 1])
         g = _C.rasterize_gaussians_backward(cam.bg, pts, radii, sc.colors.detach(), sc.scales.detach(),
                                             sc.rotations.detach(), cam.scale_modifier, self.e, cam.viewmatrix,
                                             cam.projmatrix, cam.tanfovx, cam.tanfovy, self.seed, self.e,
@@ -252,7 +383,7 @@ class BatchedFisher:
         returns None when a pose of this launch exceeded the binning capacity (its Hessian would be
         missing from the sum): the caller re-renders the chunk eagerly or rebuilds with more headroom."""
         if self.mode != "sum":
-            raise RuntimeError("built for mode='scores'")
+            raise RuntimeError(f"built for mode='{self.mode}'")
         self._load(w2cs)
         if check:
             self.status.zero_()
@@ -265,7 +396,10 @@ class BatchedFisher:
         """sum(H(w2c_k) * H_inv) for each of the (<= K) poses, float64 (one graph launch); None on a
         capacity overflow of any of them (see hessian_sum)."""
         if self.mode != "scores":
-            raise RuntimeError("built for mode='sum'")
+            raise RuntimeError(f"built for mode='{self.mode}'")
+        return self._replay_scores(w2cs, H_inv, check)
+
+    def _replay_scores(self, w2cs, H_inv, check):
         self._load(w2cs)
         with torch.no_grad():
             self.H_inv.copy_(H_inv)
@@ -275,6 +409,20 @@ class BatchedFisher:
         if check and self.overflowed(len(w2cs)):
             return None
         return self.out[:len(w2cs)].double()
+
+    def gains(self, w2cs, H_inv, k_sil: float = 1.0, k_eig: float = 1.0, k_sum: float = 1.0, nl_sil: bool = False,
+              nl_eig: bool = False, check: bool = True) -> torch.Tensor | None:
+        """send_gains' (g_sil, g_eig, gain) for each of the (<= K) poses: float64 [n,3] on the device (one graph
+        launch, then combine_gains); None on a capacity overflow of any of them (see hessian_sum).  The raw
+        counts of the launch stay in `counts[:n]`."""
+        if self.mode != "gains":
+            raise RuntimeError(f"built for mode='{self.mode}'")
+        eig = self._replay_scores(w2cs, H_inv, check)
+        if eig is None:
+            return None
+        cam = self.sc.cam
+        return combine_gains(self.counts[:len(w2cs)], eig, cam.image_width * cam.image_height, k_sil, k_eig, k_sum,
+                             nl_sil, nl_eig)
 
     def overflowed(self, n: int | None = None) -> bool:
         """True if a replay since the last status reset exceeded the capacity in one of the first `n`
