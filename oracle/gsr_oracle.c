@@ -668,6 +668,11 @@ static void chain(const oracle_in* in, const oracle_fwd_out* fo, int g, const re
 }
 
 static inline real apply_power(real v, int p) { return p == 1 ? v : RPOW(v, (real)p); }
+/* error scale of one pair's term y^p whose y = sum_q J_q g2_q is formed in floating point: with
+ * a = sum_q |J_q| |g2_q| >= |y|, the per-pair form errs by p |y|^(p-1) a and a second-moment form
+ * (sum_qr J_q J_r g2_q g2_r) by a^p, both at most p a^p */
+static inline real scale_power(real a, int p) { return p == 1 ? a : (real)p * RPOW(a, (real)p); }
+static inline real rabs(real v) { return v < 0 ? -v : v; }
 
 /* Per-pixel back-to-front pass (backward.cu:586-748 / 850-1040).  Every
  * contributing pair's terms go to the record of its (tile, Gaussian) instance
@@ -679,10 +684,11 @@ static inline real apply_power(real v, int p) { return p == 1 ? v : RPOW(v, (rea
 int oracle_backward(const oracle_in* in, const oracle_fwd_out* fo, const real* dL_dpix, int mode, int power,
                     oracle_grads* go, long long* pair_evals, long long* pair_contrib, oracle_grads* gs)
 {
-    /* gs (upstream mode, optional): per-element error scale of every gradient -- the
-     * chain's Jacobian in absolute value applied to the per-Gaussian sums of |per-pair
+    /* gs (optional): per-element error scale of every gradient; NULL skips it.  Upstream mode:
+     * the chain's Jacobian in absolute value applied to the per-Gaussian sums of |per-pair
      * term| (a float32 sum of those terms is accurate to a small multiple of
-     * eps * scale whatever the cancellation); NULL skips it. */
+     * eps * scale whatever the cancellation).  Fused mode: the sum over pairs of
+     * scale_power(|J| |per-pair term|, power), the same quantity at power 1. */
     int P = in->P, W = in->W, H = in->H;
     real fy = (real)H / ((real)2 * in->tan_fovy);
     real fx = (real)W / ((real)2 * in->tan_fovx);
@@ -699,7 +705,6 @@ int oracle_backward(const oracle_in* in, const oracle_fwd_out* fo, const real* d
     memset(go->dscales, 0, sizeof(real) * 3 * (size_t)P);
     memset(go->drot, 0, sizeof(real) * 4 * (size_t)P);
     if (gs) {
-        if (mode != GSR_ORACLE_UPSTREAM) return -1;
         memset(gs->dmeans2D, 0, sizeof(real) * 3 * (size_t)P);
         memset(gs->dcolors, 0, sizeof(real) * 3 * (size_t)P);
         memset(gs->dopacity, 0, sizeof(real) * (size_t)P);
@@ -713,7 +718,7 @@ int oracle_backward(const oracle_in* in, const oracle_fwd_out* fo, const real* d
     for (int t = 0; t < gx * gy; t++)
         if (fo->ranges[2 * t + 1] > I) I = fo->ranges[2 * t + 1];
     const int NVS = mode == GSR_ORACLE_UPSTREAM ? 9 : NV_FUSED_FIXED + 3 * nsh;
-    const int NV = (mode == GSR_ORACLE_UPSTREAM && gs) ? 18 : NVS; /* + the |term| sums */
+    const int NV = gs ? 2 * NVS : NVS; /* + the |term| sums (upstream) / the per-pair scales (fused) */
     real* rec = (real*)calloc((size_t)(I > 0 ? I : 1) * NV, sizeof(real));
     if (!rec) return -2;
     real ddelx = (real)(0.5 * W), ddely = (real)(0.5 * H);
@@ -795,6 +800,29 @@ int oracle_backward(const oracle_in* in, const oracle_fwd_out* fo, const real* d
                             }
                             r[21] += apply_power(g2[5], power);
                             for (int c = 0; c < 3 * nsh; c++) r[22 + c] += apply_power(outbuf[NOUT_FIXED + c], power);
+                            if (gs) { /* |J| |g2| per output (the chain is linear in g2), then scale_power */
+                                real A[NOUT_FIXED + 48], e9[9], col[NOUT_FIXED + 48];
+                                const int no = NOUT_FIXED + 3 * nsh;
+                                for (int o2 = 0; o2 < no; o2++) A[o2] = 0;
+                                for (int q = 0; q < 9; q++) {
+                                    if (g2[q] == 0) continue;
+                                    for (int u = 0; u < 9; u++) e9[u] = u == q ? 1 : 0;
+                                    chain(in, fo, g, e9, fx, fy, col);
+                                    for (int o2 = 0; o2 < no; o2++) A[o2] += rabs(col[o2]) * rabs(g2[q]);
+                                }
+                                real* s = r + NVS;
+                                for (int c = 0; c < 3; c++) s[c] += scale_power(rabs(g2[6 + c]), power);
+                                s[3] += scale_power(rabs(g2[0]), power);
+                                s[4] += scale_power(rabs(g2[1]), power);
+                                for (int c = 0; c < 3; c++) s[5 + c] += scale_power(A[c], power);
+                                for (int c = 0; c < 6; c++) s[8 + c] += scale_power(A[3 + c], power);
+                                if (in->scales) {
+                                    for (int c = 0; c < 3; c++) s[14 + c] += scale_power(A[9 + c], power);
+                                    for (int c = 0; c < 4; c++) s[17 + c] += scale_power(A[12 + c], power);
+                                }
+                                s[21] += scale_power(rabs(g2[5]), power);
+                                for (int c = 0; c < 3 * nsh; c++) s[22 + c] += scale_power(A[NOUT_FIXED + c], power);
+                            }
                         }
                     }
                 }
@@ -871,6 +899,19 @@ int oracle_backward(const oracle_in* in, const oracle_fwd_out* fo, const real* d
             go->dopacity[g] = a[21];
             if (go->dsh && nsh > 0)
                 for (int c = 0; c < 3 * nsh; c++) go->dsh[(size_t)3 * in->M * g + c] = a[22 + c];
+            if (gs) {
+                const real* s = a + NVS;
+                for (int c = 0; c < 3; c++) gs->dcolors[3 * g + c] = s[c];
+                gs->dmeans2D[3 * g] = s[3];
+                gs->dmeans2D[3 * g + 1] = s[4];
+                for (int c = 0; c < 3; c++) gs->dmeans3D[3 * g + c] = s[5 + c];
+                for (int c = 0; c < 6; c++) gs->dcov3D[6 * g + c] = s[8 + c];
+                for (int c = 0; c < 3; c++) gs->dscales[3 * g + c] = s[14 + c];
+                for (int c = 0; c < 4; c++) gs->drot[4 * g + c] = s[17 + c];
+                gs->dopacity[g] = s[21];
+                if (gs->dsh && nsh > 0)
+                    for (int c = 0; c < 3 * nsh; c++) gs->dsh[(size_t)3 * in->M * g + c] = s[22 + c];
+            }
         }
     }
     free(acc);

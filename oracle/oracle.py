@@ -185,10 +185,12 @@ def forward(means3D, opacities, *, view, proj, campos, tanfovx, tanfovy, H, W, b
 
 def backward(fr: ForwardResult, dL_dcolor, *, power=1, mode=UPSTREAM, error_scale=False) -> dict:
     """Reference backward; returns a dict with the 8 gradient arrays of
-    rasterize_points.cu:195 plus pair counters.  error_scale=True (upstream mode): also
+    rasterize_points.cu:195 plus pair counters.  error_scale=True: also
     g["scale"], the per-element error scale of each gradient (|Jacobian of the chain| applied
-    to each Gaussian's sums of |per-pair term|): a float32 implementation's error on an
-    element is a small multiple of eps * scale, whatever cancellation the sum has."""
+    to each Gaussian's sums of |per-pair term|; fused mode: the sum over pairs of
+    power * (|Jacobian| |per-pair term|)^power, which bounds both a per-pair powf and a
+    second-moment evaluation): a float32 implementation's error on an element is a small
+    multiple of eps * scale, whatever cancellation the sum has."""
     dtype = fr._keep["dtype"]
     lib, real, In, FwdOut, Grads = _lib(dtype)
     P = fr.radii.shape[0]
@@ -222,7 +224,7 @@ def backward(fr: ForwardResult, dL_dcolor, *, power=1, mode=UPSTREAM, error_scal
                              int(power), ctypes.byref(go), ctypes.byref(ev), ctypes.byref(ct),
                              ctypes.byref(gsp) if gsp is not None else None)
     if rc != 0:
-        raise ValueError("oracle_backward: upstream mode (and error_scale) support power == 1 only")
+        raise ValueError("oracle_backward: upstream mode supports power == 1 only")
     if error_scale:
         g["scale"] = sc
     g["pair_evals"] = ev.value

@@ -12,47 +12,11 @@ import numpy as np
 import pytest
 import torch
 
+from edge_scenes import block_of_pixel as _block_of_pixel, exact_masks as _exact_masks
 from oracle import oracle as orc
 from splatam_amd.scenes import config_scene, make_scene
 
 pytestmark = pytest.mark.gpu
-
-
-def _block_of_pixel():
-    tid = np.arange(256)
-    px = 8 * ((tid >> 6) & 1) + 4 * ((tid >> 4) & 1) + (tid & 3)
-    py = 8 * (tid >> 7) + 4 * ((tid >> 5) & 1) + ((tid >> 2) & 3)
-    return px, py, tid >> 4
-
-
-def _exact_masks(m2, co, W, H, tx, ty):
-    """float64 ellipse-vs-block masks (the kernel's construction without its margins): the alpha >= 1/255
-    ellipse's x-extent over each block row's y-span against the block columns' pixel-centre spans."""
-    ax, ay = m2[:, 0], m2[:, 1]
-    A, B, C, o = co[:, 0], co[:, 1], co[:, 2], co[:, 3]
-    det = A * C - B * B
-    tau = np.log(np.maximum(255.0 * o, 1e-30))
-    out = np.zeros(len(ax), np.int64)
-    ok = (det > 0) & (A > 0) & (tau > 0)
-    x0, y0 = 16.0 * tx, 16.0 * ty
-    with np.errstate(invalid="ignore", divide="ignore"):
-        hy = np.sqrt(2 * tau * A / det)
-        us = B * np.sqrt(2 * tau / (det * C))
-        for r in range(4):
-            lo = np.maximum(y0 + 4 * r - ay, -hy)
-            hi = np.minimum(y0 + 4 * r + 3 - ay, hy)
-            row = lo <= hi
-            ul = np.clip(us, lo, hi)
-            ur = np.clip(-us, lo, hi)
-            wl = np.sqrt(np.maximum(2 * tau * A - det * ul * ul, 0))
-            wr = np.sqrt(np.maximum(2 * tau * A - det * ur * ur, 0))
-            xmin = ax + (-B * ul - wl) / A
-            xmax = ax + (-B * ur + wr) / A
-            for c in range(4):
-                hit = ok & row & (xmax >= x0 + 4 * c) & (xmin <= x0 + 4 * c + 3)
-                bit = 4 * (2 * (r >> 1) + (c >> 1)) + 2 * (r & 1) + (c & 1)
-                out |= hit.astype(np.int64) << bit
-    return out
 
 
 @pytest.mark.parametrize("which", ["config1", "aniso"])
