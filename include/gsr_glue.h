@@ -117,6 +117,27 @@ int gsr_track_l1_fwd_bwd(int H, int W, const float* im, const float* depth_sil, 
                          const float* gt_depth, float sil_thres, float w_im, float w_depth, const float* dL_dloss,
                          float* loss, float* dL_dim, float* dL_ddepth_sil, float* scratch, void* stream);
 
+/* The loss's two weighted terms -- the `_terms` sibling of every tracking forward that writes `loss`
+ * (gsr_track_l1_fwd, gsr_track_l1_fwd_bwd, gsr_track_forward_dual_static, ..._static_xf,
+ * gsr_track_forward_backward_dual_static_xf): the same call with one more output, `terms` (device, 2 floats,
+ * 4-byte aligned, not NULL), placed after `loss`:
+ *     terms[0] = w_im * sum(mask * |gt_im - im|),  terms[1] = w_depth * sum(mask * |gt_depth - depth|)
+ * -- get_loss's weighted losses['im'] and losses['depth'] (scripts/splatam.py:262-296, :345-347); the second
+ * is what use_depth_loss_thres compares with depth_loss_thres (:748).  They are written by the thread that
+ * writes the loss, from the same two sums, with plain stores: no further reduction or atomic, the reduction
+ * scratch contract above unchanged.  loss keeps its own expression (w_im * s0 + w_depth * s1, which the
+ * compiler may contract), so terms[0] + terms[1] may differ from it in the last bit; every other output is
+ * bitwise that of the sibling without terms.  Wherever the loss is invalid (a static forward that overflowed)
+ * so are the terms.  A NULL or misaligned `terms` is GSR_ERR_INVALID_ARG, reported before the sibling's own
+ * checks, which follow unchanged (under the sibling's name in gsr_last_error). */
+int gsr_track_l1_fwd_terms(int H, int W, const float* im, const float* depth_sil, const float* gt_im,
+                           const float* gt_depth, float sil_thres, float w_im, float w_depth, float* loss,
+                           float* terms, float* scratch, void* stream);
+int gsr_track_l1_fwd_bwd_terms(int H, int W, const float* im, const float* depth_sil, const float* gt_im,
+                               const float* gt_depth, float sil_thres, float w_im, float w_depth,
+                               const float* dL_dloss, float* loss, float* terms, float* dL_dim, float* dL_ddepth_sil,
+                               float* scratch, void* stream);
+
 /* dL_dloss: 1 float (device).  Writes dL_dim [3,H,W] and dL_ddepth_sil [3,H,W]. */
 int gsr_track_l1_bwd(int H, int W, const float* im, const float* depth_sil, const float* gt_im,
                      const float* gt_depth, float sil_thres, float w_im, float w_depth, const float* dL_dloss,
@@ -137,6 +158,14 @@ int gsr_track_forward_dual_static(const gsr_settings* settings, const gsr_gaussi
                                   float sil_thres, float w_im, float w_depth, const float* dL_dloss, float* loss,
                                   float* dL_dim, float* dL_ddepth_sil, float* scratch, gsr_alloc_fn alloc,
                                   void* alloc_ctx, void* stream);
+/* ... with the loss's two terms (gsr_track_l1_fwd_terms above); an empty map (P == 0) writes them as zero. */
+int gsr_track_forward_dual_static_terms(const gsr_settings* settings, const gsr_gaussians* gaussians,
+                                        const float* colors2, int capacity, unsigned* status, float* out_color,
+                                        float* out_color2, float* out_depth, int* radii, const float* gt_im,
+                                        const float* gt_depth, float sil_thres, float w_im, float w_depth,
+                                        const float* dL_dloss, float* loss, float* terms, float* dL_dim,
+                                        float* dL_ddepth_sil, float* scratch, gsr_alloc_fn alloc, void* alloc_ctx,
+                                        void* stream);
 
 /* gsr_track_transform_fwd fused into gsr_track_forward_dual_static (SURVEY.md 8(f) row 3:
  * "transform-to-frame plus the [z,1,z^2] colours fused into preprocess"): the rasterizer's
@@ -172,6 +201,13 @@ int gsr_track_forward_dual_static_xf(const gsr_settings* settings, const gsr_gau
                                      const float* gt_depth, float sil_thres, float w_im, float w_depth,
                                      const float* dL_dloss, float* loss, float* dL_dim, float* dL_ddepth_sil,
                                      float* scratch, gsr_alloc_fn alloc, void* alloc_ctx, void* stream);
+int gsr_track_forward_dual_static_xf_terms(const gsr_settings* settings, const gsr_gaussians* gaussians,
+                                           float* colors2, const gsr_track_xform* xform, int capacity,
+                                           unsigned* status, float* out_color, float* out_color2, float* out_depth,
+                                           int* radii, const float* gt_im, const float* gt_depth, float sil_thres,
+                                           float w_im, float w_depth, const float* dL_dloss, float* loss,
+                                           float* terms, float* dL_dim, float* dL_ddepth_sil, float* scratch,
+                                           gsr_alloc_fn alloc, void* alloc_ctx, void* stream);
 
 /* Tracking backward with the pose chain fused into the rasterizer's per-Gaussian
  * backward: gsr_backward_dual's render backward (depth channel of the second
@@ -225,6 +261,14 @@ int gsr_track_forward_backward_dual_static_xf(const gsr_settings* settings, cons
                                               const float* dL_dloss, float* loss, float* scratch,
                                               float* inst_records, gsr_alloc_fn alloc, void* alloc_ctx,
                                               void* stream);
+int gsr_track_forward_backward_dual_static_xf_terms(const gsr_settings* settings, const gsr_gaussians* gaussians,
+                                                    float* colors2, const gsr_track_xform* xform, int capacity,
+                                                    unsigned* status, float* out_color, float* out_color2,
+                                                    float* out_depth, int* radii, const float* gt_im,
+                                                    const float* gt_depth, float sil_thres, float w_im,
+                                                    float w_depth, const float* dL_dloss, float* loss, float* terms,
+                                                    float* scratch, float* inst_records, gsr_alloc_fn alloc,
+                                                    void* alloc_ctx, void* stream);
 /* gsr_track_backward_dual after gsr_track_forward_backward_dual_static_xf: only the pose-fused
  * per-Gaussian backward (the render backward's records come from inst_records). */
 int gsr_track_backward_dual_records(const gsr_settings* settings, const gsr_gaussians* gaussians, const int* radii,

@@ -618,9 +618,17 @@ def track_backward_dual(settings, means3D, radii, colors, colors2, scales, rotat
         _tls.buffers = {}
 
 
+def terms_ptr(terms: torch.Tensor, device) -> int:
+    """The address of a `terms` output (the gsr_track_*_terms entries): two contiguous float32 on `device`."""
+    if (not torch.is_tensor(terms) or terms.device != device or terms.dtype != torch.float32 or
+            terms.numel() != 2 or not terms.is_contiguous()):
+        raise RuntimeError("terms: a contiguous float32 tensor of 2 elements on the forward's device")
+    return terms.data_ptr()
+
+
 def track_forward_dual_static(settings, means3D, colors, colors2, opacity, scales, rotations, capacity, status, gt_im,
                               gt_depth, sil_thres, w_im, w_depth, seed, scratch, xform=None, records=None,
-                              images=True):
+                              images=True, terms=None):
     """gsr_track_forward_dual_static (include/gsr_glue.h): the static dual forward with SplaTAM's
     tracking L1 loss and its gradient images formed in the render epilogue.  Returns (num_rendered=capacity,
     color, color2, radii, geomBuffer, binningBuffer, imgBuffer, depth, loss, dL_dim, dL_ddepth_sil).
@@ -631,7 +639,9 @@ def track_forward_dual_static(settings, means3D, colors, colors2, opacity, scale
     gsr_track_forward_backward_dual_static_xf -- the tracking render backward runs in the same launch
     and leaves its per-instance sums in records (track_backward_dual(records=...)); dL_dim / dL_ddepth_sil
     come back None (not formed).  images=False (with records): the rendered images are not stored either
-    (color, color2 and depth come back None; the loss and the backward consume them in registers)."""
+    (color, color2 and depth come back None; the loss and the backward consume them in registers).
+    terms (device float32, 2 elements): the call's _terms sibling -- the loss's two weighted terms
+    (w_im * image sum, w_depth * depth sum) are written there next to the loss."""
     st = settings
     device = means3D.device
     P = means3D.size(0)
@@ -657,6 +667,8 @@ def track_forward_dual_static(settings, means3D, colors, colors2, opacity, scale
             dim, dds = torch.empty(3, H, W, **f32), torch.empty(3, H, W, **f32)
         if status is None or status.device != device or status.numel() < 4:
             raise RuntimeError("static dual forward needs a device status tensor of 4 int32")
+        # the _terms sibling of each call: `terms` behind `loss`
+        tp = () if terms is None else (terms_ptr(terms, device),)
         _begin(device)
         if xform is not None:
             outs = (means3D, colors2, opacity, scales, rotations)
@@ -676,26 +688,29 @@ def track_forward_dual_static(settings, means3D, colors, colors2, opacity, scale
                 if (records.device != device or records.dtype != torch.float32 or not records.is_contiguous() or
                         records.numel() < lib.gsr_track_records_floats(int(capacity))):
                     raise RuntimeError("records: contiguous float32 of gsr_track_records_floats(capacity) on the device")
-                n = lib.gsr_track_forward_backward_dual_static_xf(
+                fn = lib.gsr_track_forward_backward_dual_static_xf_terms if tp else \
+                    lib.gsr_track_forward_backward_dual_static_xf
+                n = fn(
                     ctypes.byref(s), ctypes.byref(g), _ptr(c2), ctypes.byref(xf), int(capacity), status.data_ptr(),
                     _ptr(out_color), _ptr(out_color2), _ptr(out_depth), radii.data_ptr() if P else None,
                     gi.data_ptr(), gd.data_ptr(), float(sil_thres), float(w_im), float(w_depth), sd.data_ptr(),
-                    loss.data_ptr(), scratch.data_ptr(), records.data_ptr(), _ALLOC_CB, None, _stream(device))
+                    loss.data_ptr(), *tp, scratch.data_ptr(), records.data_ptr(), _ALLOC_CB, None, _stream(device))
                 _check(n, "track_forward_backward_dual_static_xf")
                 bufs = _tls.buffers
                 return (int(n), out_color, out_color2, radii, bufs[0], bufs[1], bufs[2], out_depth, loss, None, None)
-            n = lib.gsr_track_forward_dual_static_xf(
+            n = (lib.gsr_track_forward_dual_static_xf_terms if tp else lib.gsr_track_forward_dual_static_xf)(
                 ctypes.byref(s), ctypes.byref(g), _ptr(c2), ctypes.byref(xf), int(capacity), status.data_ptr(),
                 out_color.data_ptr(), out_color2.data_ptr(), out_depth.data_ptr(), radii.data_ptr() if P else None,
                 gi.data_ptr(), gd.data_ptr(), float(sil_thres), float(w_im), float(w_depth), sd.data_ptr(),
-                loss.data_ptr(), dim.data_ptr(), dds.data_ptr(), scratch.data_ptr(), _ALLOC_CB, None, _stream(device))
+                loss.data_ptr(), *tp, dim.data_ptr(), dds.data_ptr(), scratch.data_ptr(), _ALLOC_CB, None,
+                _stream(device))
             _check(n, "track_forward_dual_static_xf")
             bufs = _tls.buffers
             return (int(n), out_color, out_color2, radii, bufs[0], bufs[1], bufs[2], out_depth, loss, dim, dds)
-        n = lib.gsr_track_forward_dual_static(
+        n = (lib.gsr_track_forward_dual_static_terms if tp else lib.gsr_track_forward_dual_static)(
             ctypes.byref(s), ctypes.byref(g), _ptr(c2), int(capacity), status.data_ptr(), out_color.data_ptr(),
             out_color2.data_ptr(), out_depth.data_ptr(), radii.data_ptr() if P else None, gi.data_ptr(),
-            gd.data_ptr(), float(sil_thres), float(w_im), float(w_depth), sd.data_ptr(), loss.data_ptr(),
+            gd.data_ptr(), float(sil_thres), float(w_im), float(w_depth), sd.data_ptr(), loss.data_ptr(), *tp,
             dim.data_ptr(), dds.data_ptr(), scratch.data_ptr(), _ALLOC_CB, None, _stream(device))
         _check(n, "track_forward_dual_static")
         bufs = _tls.buffers

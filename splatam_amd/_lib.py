@@ -125,6 +125,29 @@ SIGNATURES = {
                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float,
                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ALLOC_FN, c_void_p,
                                                  c_void_p]),
+    # the _terms siblings: one more pointer (`terms`) behind `loss`
+    "gsr_track_l1_fwd_terms": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float,
+                                       ctypes.c_float, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gsr_track_l1_fwd_bwd_terms": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float,
+                                           ctypes.c_float, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
+    "gsr_track_forward_dual_static_terms": (c_int, [ctypes.POINTER(GsrSettings), ctypes.POINTER(GsrGaussians),
+                                                    c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p, ALLOC_FN, c_void_p,
+                                                    c_void_p]),
+    "gsr_track_forward_dual_static_xf_terms": (c_int, [ctypes.POINTER(GsrSettings), ctypes.POINTER(GsrGaussians),
+                                                       c_void_p, ctypes.POINTER(GsrTrackXform), c_int, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                       c_float, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p, ALLOC_FN, c_void_p, c_void_p]),
+    "gsr_track_forward_backward_dual_static_xf_terms": (c_int, [ctypes.POINTER(GsrSettings),
+                                                                ctypes.POINTER(GsrGaussians), c_void_p,
+                                                                ctypes.POINTER(GsrTrackXform), c_int, c_void_p,
+                                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                                c_void_p, c_float, c_float, c_float, c_void_p,
+                                                                c_void_p, c_void_p, c_void_p, c_void_p, ALLOC_FN,
+                                                                c_void_p, c_void_p]),
     "gsr_track_records_floats": (c_int, [c_int]),
     "gsr_track_forward_backward_dual_static_xf": (c_int, [ctypes.POINTER(GsrSettings), ctypes.POINTER(GsrGaussians),
                                                           c_void_p, ctypes.POINTER(GsrTrackXform), c_int, c_void_p,

@@ -46,6 +46,13 @@ int hip_fail(hipError_t e, const char* where) {
     return fail(GSR_ERR_HIP, std::string(where) + ": " + hipGetErrorString(e));
 }
 
+int check_terms(const char* entry, const float* terms) {
+    if (!terms) return fail(GSR_ERR_INVALID_ARG, std::string(entry) + ": null terms");
+    if ((uintptr_t)terms % sizeof(float) != 0)
+        return fail(GSR_ERR_INVALID_ARG, std::string(entry) + ": terms must be 4-byte aligned");
+    return GSR_OK;
+}
+
 int stream_device(hipStream_t s) {
     thread_local hipStream_t last_s = nullptr;
     thread_local int last_d = -1;
@@ -348,6 +355,7 @@ struct Forward {
         const size_t img3 = sizeof(float) * 3 * (size_t)W * H;
         if (const TrackL1* l1 = c.l1) {  // the zero silhouette masks every pixel: loss 0 and zero gradient images
             if ((e = zero_async(l1->loss, sizeof(float), stream)) != hipSuccess ||
+                (l1->terms && (e = zero_async(l1->terms, 2 * sizeof(float), stream)) != hipSuccess) ||
                 (l1->dL_dim && (e = zero_async(l1->dL_dim, img3, stream)) != hipSuccess) ||
                 (l1->dL_dds && (e = zero_async(l1->dL_dds, img3, stream)) != hipSuccess))
                 return hip_fail(e, "zero loss");
@@ -980,19 +988,41 @@ int gsr_track_forward_scratch_floats(int image_width, int image_height) {
     return track_l1_fused_scratch_floats(gx * gy > 0 ? gx * gy : 1);
 }
 
+// The three tracking forwards and their _terms siblings share one body each: `terms` NULL is the entry without
+// them (the kernels then take today's path), and a sibling's own check (check_terms) comes before the shared ones.
+static int track_forward_static(FwdCall c, const float* colors2, float* out_color2, int capacity, unsigned* status,
+                                const TrackL1& l1) {
+    if (int rc = check_dual_static(colors2, capacity, status)) return rc;
+    if (!l1.gt_im || !l1.gt_depth || !l1.seed || !l1.loss || !l1.dL_dim || !l1.dL_dds || !l1.scratch)
+        return fail(GSR_ERR_INVALID_ARG, "track_forward_dual_static: null pointer");
+    c.l1 = &l1;
+    return forward_impl(statics(dual(c, colors2, out_color2), capacity, status));
+}
+
 int gsr_track_forward_dual_static(const gsr_settings* settings, const gsr_gaussians* gaussians, const float* colors2,
                                   int capacity, unsigned* status, float* out_color, float* out_color2,
                                   float* out_depth, int* radii, const float* gt_im, const float* gt_depth,
                                   float sil_thres, float w_im, float w_depth, const float* dL_dloss, float* loss,
                                   float* dL_dim, float* dL_ddepth_sil, float* scratch, gsr_alloc_fn alloc,
                                   void* alloc_ctx, void* stream) {
-    if (int rc = check_dual_static(colors2, capacity, status)) return rc;
-    if (!gt_im || !gt_depth || !dL_dloss || !loss || !dL_dim || !dL_ddepth_sil || !scratch)
-        return fail(GSR_ERR_INVALID_ARG, "track_forward_dual_static: null pointer");
-    const TrackL1 l1{gt_im, gt_depth, sil_thres, w_im, w_depth, dL_dloss, dL_dim, dL_ddepth_sil, scratch, loss};
-    FwdCall c = fwd_call(settings, gaussians, out_color, out_depth, radii, alloc, alloc_ctx, stream);
-    c.l1 = &l1;
-    return forward_impl(statics(dual(c, colors2, out_color2), capacity, status));
+    return track_forward_static(
+        fwd_call(settings, gaussians, out_color, out_depth, radii, alloc, alloc_ctx, stream), colors2, out_color2,
+        capacity, status,
+        TrackL1{gt_im, gt_depth, sil_thres, w_im, w_depth, dL_dloss, dL_dim, dL_ddepth_sil, scratch, loss, nullptr});
+}
+
+int gsr_track_forward_dual_static_terms(const gsr_settings* settings, const gsr_gaussians* gaussians,
+                                        const float* colors2, int capacity, unsigned* status, float* out_color,
+                                        float* out_color2, float* out_depth, int* radii, const float* gt_im,
+                                        const float* gt_depth, float sil_thres, float w_im, float w_depth,
+                                        const float* dL_dloss, float* loss, float* terms, float* dL_dim,
+                                        float* dL_ddepth_sil, float* scratch, gsr_alloc_fn alloc, void* alloc_ctx,
+                                        void* stream) {
+    if (int rc = check_terms("track_forward_dual_static_terms", terms)) return rc;
+    return track_forward_static(
+        fwd_call(settings, gaussians, out_color, out_depth, radii, alloc, alloc_ctx, stream), colors2, out_color2,
+        capacity, status,
+        TrackL1{gt_im, gt_depth, sil_thres, w_im, w_depth, dL_dloss, dL_dim, dL_ddepth_sil, scratch, loss, terms});
 }
 
 int gsr_track_forward_dual_static_xf(const gsr_settings* settings, const gsr_gaussians* gaussians, float* colors2,
@@ -1005,10 +1035,36 @@ int gsr_track_forward_dual_static_xf(const gsr_settings* settings, const gsr_gau
     statics(dual(c, colors2, out_color2), capacity, status);
     return track_forward_xf(c, xform,
                             TrackL1{gt_im, gt_depth, sil_thres, w_im, w_depth, dL_dloss, dL_dim, dL_ddepth_sil,
-                                    scratch, loss});
+                                    scratch, loss, nullptr});
+}
+
+int gsr_track_forward_dual_static_xf_terms(const gsr_settings* settings, const gsr_gaussians* gaussians,
+                                           float* colors2, const gsr_track_xform* xform, int capacity,
+                                           unsigned* status, float* out_color, float* out_color2, float* out_depth,
+                                           int* radii, const float* gt_im, const float* gt_depth, float sil_thres,
+                                           float w_im, float w_depth, const float* dL_dloss, float* loss,
+                                           float* terms, float* dL_dim, float* dL_ddepth_sil, float* scratch,
+                                           gsr_alloc_fn alloc, void* alloc_ctx, void* stream) {
+    if (int rc = check_terms("track_forward_dual_static_xf_terms", terms)) return rc;
+    FwdCall c = fwd_call(settings, gaussians, out_color, out_depth, radii, alloc, alloc_ctx, stream);
+    statics(dual(c, colors2, out_color2), capacity, status);
+    return track_forward_xf(c, xform,
+                            TrackL1{gt_im, gt_depth, sil_thres, w_im, w_depth, dL_dloss, dL_dim, dL_ddepth_sil,
+                                    scratch, loss, terms});
 }
 
 int gsr_track_records_floats(int capacity) { return track_records_stride() * (capacity > 1 ? capacity : 1); }
+
+// gsr_track_forward_backward_dual_static_xf(_terms)
+static int track_forward_backward_xf(FwdCall c, float* colors2, float* out_color2, const gsr_track_xform* xform,
+                                     int capacity, unsigned* status, float* inst_records, const TrackL1& l1) {
+    if (!inst_records) return fail(GSR_ERR_INVALID_ARG, "track_forward_backward_dual_static_xf: null records");
+    // the gradient images are not formed (the backward runs from the registers); the L1 epilogue's
+    // pointers to them are never dereferenced.  out_color, out_color2 and out_depth all NULL: the rendered
+    // images (and final_T / n_contrib / the block maxima of the image buffer) are not stored either
+    statics(dual(c, colors2, out_color2), capacity, status).track_inst = inst_records;
+    return track_forward_xf(c, xform, l1);
+}
 
 int gsr_track_forward_backward_dual_static_xf(const gsr_settings* settings, const gsr_gaussians* gaussians,
                                               float* colors2, const gsr_track_xform* xform, int capacity,
@@ -1018,15 +1074,25 @@ int gsr_track_forward_backward_dual_static_xf(const gsr_settings* settings, cons
                                               const float* dL_dloss, float* loss, float* scratch,
                                               float* inst_records, gsr_alloc_fn alloc, void* alloc_ctx,
                                               void* stream) {
-    if (!inst_records) return fail(GSR_ERR_INVALID_ARG, "track_forward_backward_dual_static_xf: null records");
-    // the gradient images are not formed (the backward runs from the registers); the L1 epilogue's
-    // pointers to them are never dereferenced.  out_color, out_color2 and out_depth all NULL: the rendered
-    // images (and final_T / n_contrib / the block maxima of the image buffer) are not stored either
-    FwdCall c = fwd_call(settings, gaussians, out_color, out_depth, radii, alloc, alloc_ctx, stream);
-    statics(dual(c, colors2, out_color2), capacity, status).track_inst = inst_records;
-    return track_forward_xf(c, xform,
-                            TrackL1{gt_im, gt_depth, sil_thres, w_im, w_depth, dL_dloss, nullptr, nullptr, scratch,
-                                    loss});
+    return track_forward_backward_xf(
+        fwd_call(settings, gaussians, out_color, out_depth, radii, alloc, alloc_ctx, stream), colors2, out_color2,
+        xform, capacity, status, inst_records,
+        TrackL1{gt_im, gt_depth, sil_thres, w_im, w_depth, dL_dloss, nullptr, nullptr, scratch, loss, nullptr});
+}
+
+int gsr_track_forward_backward_dual_static_xf_terms(const gsr_settings* settings, const gsr_gaussians* gaussians,
+                                                    float* colors2, const gsr_track_xform* xform, int capacity,
+                                                    unsigned* status, float* out_color, float* out_color2,
+                                                    float* out_depth, int* radii, const float* gt_im,
+                                                    const float* gt_depth, float sil_thres, float w_im,
+                                                    float w_depth, const float* dL_dloss, float* loss, float* terms,
+                                                    float* scratch, float* inst_records, gsr_alloc_fn alloc,
+                                                    void* alloc_ctx, void* stream) {
+    if (int rc = check_terms("track_forward_backward_dual_static_xf_terms", terms)) return rc;
+    return track_forward_backward_xf(
+        fwd_call(settings, gaussians, out_color, out_depth, radii, alloc, alloc_ctx, stream), colors2, out_color2,
+        xform, capacity, status, inst_records,
+        TrackL1{gt_im, gt_depth, sil_thres, w_im, w_depth, dL_dloss, nullptr, nullptr, scratch, loss, terms});
 }
 
 int gsr_forward_reuse(const gsr_settings* settings, const gsr_gaussians* gaussians, int num_rendered,

@@ -1277,6 +1277,7 @@ struct TrackL1 {
     float* dL_dds;          // [3,H,W] (channels 1, 2 written as zero)
     float* scratch;         // arrival counters (zero between launches), then 2 partials per tile
     float* loss;            // device scalar
+    float* terms;           // NULL, or 2 floats next to the loss: {w_im * image sum, w_depth * depth sum}
 };
 int track_l1_fused_scratch_floats(int ntiles);
 // keys: the unsorted tile buckets (render_fwd sorts each tile's bucket into point_list in
@@ -1437,6 +1438,8 @@ int hip_fail(hipError_t e, const char* where);
 // the sequence steps' argument tests: an image whose pixel index fits an int, a workspace's alignment
 inline bool image_size_ok(int H, int W) { return H > 0 && W > 0 && (long long)H * W <= 0x7fffffffLL; }
 inline bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+// the `terms` output of the gsr_track_*_terms entries (two floats): not NULL, 4-byte aligned (gsr_capi.hip)
+int check_terms(const char* entry, const float* terms);
 // backward_power != 1 (the vendored renderCUDAFused semantics, backward.cu:850-1140)
 // backward_power == 2 through per-instance second moments (gsr_backward.hip, gauss_bwd_mom_kernel)
 int moments_record_floats(bool sh);

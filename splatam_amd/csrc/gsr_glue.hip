@@ -90,15 +90,15 @@ track_transform_bwd_kernel(int P, const float* __restrict__ mw, const float* __r
 }
 
 // Masked L1 loss in one launch: per-workgroup partial sums published, the last
-// workgroup adds them in a fixed order and writes the loss.  With dloss, the
-// gradient images are written in the same pass (g = *dloss, read now: the
+// workgroup adds them in a fixed order and writes the loss (and, with terms,
+// its two weighted terms).  With dloss, the gradient images are written in the same pass (g = *dloss, read now: the
 // caller's loss seed must already hold its value).  scratch: the arrival counters
 // (zero before the first launch; left zero), then 4 * gridDim.x partials.
 __global__ void __launch_bounds__(GLUE_BLOCK)
 track_l1_kernel(int HW, const float* __restrict__ im, const float* __restrict__ ds,
                 const float* __restrict__ gt_im, const float* __restrict__ gt_d, float thres, float w_im,
                 float w_depth, float* __restrict__ scratch, float* __restrict__ loss, const float* __restrict__ dloss,
-                float* __restrict__ dim, float* __restrict__ dds) {
+                float* __restrict__ dim, float* __restrict__ dds, float* __restrict__ terms) {
     __shared__ float s_red[4 * 4];
     __shared__ float s_tot[4];
     const float g = dloss ? dloss[0] : 0.f;
@@ -135,7 +135,13 @@ track_l1_kernel(int HW, const float* __restrict__ im, const float* __restrict__ 
     __syncthreads();
     block_sum<4>(v, s_red, s_tot);
     __syncthreads();
-    if (threadIdx.x == 0) loss[0] = w_im * s_tot[0] + w_depth * s_tot[1];
+    if (threadIdx.x == 0) {
+        loss[0] = w_im * s_tot[0] + w_depth * s_tot[1];
+        if (terms) {  // the loss's two weighted terms (get_loss's losses['im'], losses['depth'])
+            terms[0] = w_im * s_tot[0];
+            terms[1] = w_depth * s_tot[1];
+        }
+    }
 }
 
 __global__ void __launch_bounds__(GLUE_BLOCK)
@@ -251,31 +257,65 @@ int gsr_track_transform_bwd_adam(int P, const float* means_world, const float* u
     return e == hipSuccess ? GSR_OK : hip_fail(e, "track_transform_bwd_adam");
 }
 
-int gsr_track_l1_fwd(int H, int W, const float* im, const float* depth_sil, const float* gt_im,
-                     const float* gt_depth, float sil_thres, float w_im, float w_depth, float* loss, float* scratch,
-                     void* stream) {
+// gsr_track_l1_fwd(_terms): terms NULL = the entry without them
+static int track_l1_fwd(int H, int W, const float* im, const float* depth_sil, const float* gt_im,
+                        const float* gt_depth, float sil_thres, float w_im, float w_depth, float* loss, float* terms,
+                        float* scratch, void* stream) {
     if (H <= 0 || W <= 0) return fail(GSR_ERR_INVALID_ARG, "track_l1_fwd: bad image size");
     if (!im || !depth_sil || !gt_im || !gt_depth || !loss || !scratch)
         return fail(GSR_ERR_INVALID_ARG, "track_l1_fwd: null pointer");
     const int HW = H * W;
     hipLaunchKernelGGL(track_l1_kernel, dim3(blocks_for(HW)), dim3(GLUE_BLOCK), 0, (hipStream_t)stream, HW, im,
-                       depth_sil, gt_im, gt_depth, sil_thres, w_im, w_depth, scratch, loss, nullptr, nullptr, nullptr);
+                       depth_sil, gt_im, gt_depth, sil_thres, w_im, w_depth, scratch, loss, nullptr, nullptr, nullptr,
+                       terms);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? GSR_OK : hip_fail(e, "track_l1_fwd");
 }
 
-int gsr_track_l1_fwd_bwd(int H, int W, const float* im, const float* depth_sil, const float* gt_im,
-                         const float* gt_depth, float sil_thres, float w_im, float w_depth, const float* dL_dloss,
-                         float* loss, float* dL_dim, float* dL_ddepth_sil, float* scratch, void* stream) {
+int gsr_track_l1_fwd(int H, int W, const float* im, const float* depth_sil, const float* gt_im,
+                     const float* gt_depth, float sil_thres, float w_im, float w_depth, float* loss, float* scratch,
+                     void* stream) {
+    return track_l1_fwd(H, W, im, depth_sil, gt_im, gt_depth, sil_thres, w_im, w_depth, loss, nullptr, scratch,
+                        stream);
+}
+
+int gsr_track_l1_fwd_terms(int H, int W, const float* im, const float* depth_sil, const float* gt_im,
+                           const float* gt_depth, float sil_thres, float w_im, float w_depth, float* loss,
+                           float* terms, float* scratch, void* stream) {
+    if (int rc = check_terms("track_l1_fwd_terms", terms)) return rc;
+    return track_l1_fwd(H, W, im, depth_sil, gt_im, gt_depth, sil_thres, w_im, w_depth, loss, terms, scratch, stream);
+}
+
+// gsr_track_l1_fwd_bwd(_terms)
+static int track_l1_fwd_bwd(int H, int W, const float* im, const float* depth_sil, const float* gt_im,
+                            const float* gt_depth, float sil_thres, float w_im, float w_depth, const float* dL_dloss,
+                            float* loss, float* terms, float* dL_dim, float* dL_ddepth_sil, float* scratch,
+                            void* stream) {
     if (H <= 0 || W <= 0) return fail(GSR_ERR_INVALID_ARG, "track_l1_fwd_bwd: bad image size");
     if (!im || !depth_sil || !gt_im || !gt_depth || !loss || !scratch || !dL_dloss || !dL_dim || !dL_ddepth_sil)
         return fail(GSR_ERR_INVALID_ARG, "track_l1_fwd_bwd: null pointer");
     const int HW = H * W;
     hipLaunchKernelGGL(track_l1_kernel, dim3(blocks_for(HW)), dim3(GLUE_BLOCK), 0, (hipStream_t)stream, HW, im,
                        depth_sil, gt_im, gt_depth, sil_thres, w_im, w_depth, scratch, loss, dL_dloss, dL_dim,
-                       dL_ddepth_sil);
+                       dL_ddepth_sil, terms);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? GSR_OK : hip_fail(e, "track_l1_fwd_bwd");
+}
+
+int gsr_track_l1_fwd_bwd(int H, int W, const float* im, const float* depth_sil, const float* gt_im,
+                         const float* gt_depth, float sil_thres, float w_im, float w_depth, const float* dL_dloss,
+                         float* loss, float* dL_dim, float* dL_ddepth_sil, float* scratch, void* stream) {
+    return track_l1_fwd_bwd(H, W, im, depth_sil, gt_im, gt_depth, sil_thres, w_im, w_depth, dL_dloss, loss, nullptr,
+                            dL_dim, dL_ddepth_sil, scratch, stream);
+}
+
+int gsr_track_l1_fwd_bwd_terms(int H, int W, const float* im, const float* depth_sil, const float* gt_im,
+                               const float* gt_depth, float sil_thres, float w_im, float w_depth,
+                               const float* dL_dloss, float* loss, float* terms, float* dL_dim, float* dL_ddepth_sil,
+                               float* scratch, void* stream) {
+    if (int rc = check_terms("track_l1_fwd_bwd_terms", terms)) return rc;
+    return track_l1_fwd_bwd(H, W, im, depth_sil, gt_im, gt_depth, sil_thres, w_im, w_depth, dL_dloss, loss, terms,
+                            dL_dim, dL_ddepth_sil, scratch, stream);
 }
 
 int gsr_track_l1_bwd(int H, int W, const float* im, const float* depth_sil, const float* gt_im,

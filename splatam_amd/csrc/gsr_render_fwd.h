@@ -446,6 +446,10 @@ __device__ __forceinline__ void l1_finish(const TrackL1& l1) {
             const float s0 = (s_fin[0] + s_fin[4]) + (s_fin[8] + s_fin[12]);
             const float s1 = (s_fin[1] + s_fin[5]) + (s_fin[9] + s_fin[13]);
             l1.loss[0] = l1.w_im * s0 + l1.w_depth * s1;
+            if (l1.terms) {  // the loss's two weighted terms (get_loss's losses['im'], losses['depth'])
+                l1.terms[0] = l1.w_im * s0;
+                l1.terms[1] = l1.w_depth * s1;
+            }
         }
     }
 }

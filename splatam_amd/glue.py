@@ -193,9 +193,27 @@ def track_transform(params: dict, time_idx: int, w2c: torch.Tensor, pose_adam: P
                                  params["log_scales"].detach(), w2c, int(time_idx), pose_adam)
 
 
+def _track_l1(H, W, im, ds, gt_im, gt_d, sil_thres, w_im, w_depth, seed, loss, terms, dim, dds, scratch):
+    """The stand-alone tracking L1 launch: gsr_track_l1_fwd, or with `seed` (and the gradient images dim / dds)
+    gsr_track_l1_fwd_bwd; with `terms` (device float32 [2]) the _terms sibling of either."""
+    from ._C import terms_ptr
+    head = (H, W, im.data_ptr(), ds.data_ptr(), gt_im.data_ptr(), gt_d.data_ptr(), float(sil_thres), float(w_im),
+            float(w_depth))
+    tp = () if terms is None else (terms_ptr(terms, im.device),)
+    if seed is not None:
+        fn = lib.gsr_track_l1_fwd_bwd_terms if tp else lib.gsr_track_l1_fwd_bwd
+        rc = fn(*head, seed.data_ptr(), loss.data_ptr(), *tp, dim.data_ptr(), dds.data_ptr(), scratch.data_ptr(),
+                _stream(im))
+        _check(rc, "track_l1_fwd_bwd")
+    else:
+        fn = lib.gsr_track_l1_fwd_terms if tp else lib.gsr_track_l1_fwd
+        rc = fn(*head, loss.data_ptr(), *tp, scratch.data_ptr(), _stream(im))
+        _check(rc, "track_l1_fwd")
+
+
 class _TrackingL1(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, im, depth_sil, gt_im, gt_depth, sil_thres, w_im, w_depth, seed=None):
+    def forward(ctx, im, depth_sil, gt_im, gt_depth, sil_thres, w_im, w_depth, seed=None, terms=None):
         im, depth_sil = _f32c(im, "im"), _f32c(depth_sil, "depth_sil")
         gt_im, gt_depth = _f32c(gt_im, "gt_im"), _f32c(gt_depth, "gt_depth")
         _, H, W = im.shape
@@ -204,20 +222,12 @@ class _TrackingL1(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=im.device)
         scratch = _scratch(im, lib.gsr_track_scratch_floats(H * W))
         ctx.pre = None
+        dim = dds = None
         if seed is not None:  # the caller's static loss seed: gradient images in the same pass
             seed = _f32c(seed, "seed")
             dim, dds = torch.empty_like(im), torch.empty_like(depth_sil)
-            rc = lib.gsr_track_l1_fwd_bwd(H, W, im.data_ptr(), depth_sil.data_ptr(), gt_im.data_ptr(),
-                                          gt_depth.data_ptr(), float(sil_thres), float(w_im), float(w_depth),
-                                          seed.data_ptr(), loss.data_ptr(), dim.data_ptr(), dds.data_ptr(),
-                                          scratch.data_ptr(), _stream(im))
-            _check(rc, "track_l1_fwd_bwd")
             ctx.pre = (dim, dds, seed)  # the seed stays referenced: its address cannot be reused
-        else:
-            rc = lib.gsr_track_l1_fwd(H, W, im.data_ptr(), depth_sil.data_ptr(), gt_im.data_ptr(),
-                                      gt_depth.data_ptr(), float(sil_thres), float(w_im), float(w_depth),
-                                      loss.data_ptr(), scratch.data_ptr(), _stream(im))
-            _check(rc, "track_l1_fwd")
+        _track_l1(H, W, im, depth_sil, gt_im, gt_depth, sil_thres, w_im, w_depth, seed, loss, terms, dim, dds, scratch)
         ctx.save_for_backward(im, depth_sil, gt_im, gt_depth)
         ctx.meta = (float(sil_thres), float(w_im), float(w_depth))
         return loss
@@ -225,7 +235,7 @@ class _TrackingL1(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         if ctx.pre is not None and g.data_ptr() == ctx.pre[2].data_ptr():  # seeded with the forward's seed
-            return ctx.pre[0], ctx.pre[1], None, None, None, None, None, None
+            return ctx.pre[0], ctx.pre[1], None, None, None, None, None, None, None
         im, depth_sil, gt_im, gt_depth = ctx.saved_tensors
         sil_thres, w_im, w_depth = ctx.meta
         _, H, W = im.shape
@@ -235,17 +245,19 @@ class _TrackingL1(torch.autograd.Function):
         rc = lib.gsr_track_l1_bwd(H, W, im.data_ptr(), depth_sil.data_ptr(), gt_im.data_ptr(), gt_depth.data_ptr(),
                                   sil_thres, w_im, w_depth, g.data_ptr(), dim.data_ptr(), dds.data_ptr(), _stream(im))
         _check(rc, "track_l1_bwd")
-        return dim, dds, None, None, None, None, None, None
+        return dim, dds, None, None, None, None, None, None, None
 
 
-def tracking_l1(im, depth_sil, gt_im, gt_depth, sil_thres=0.99, w_im=0.5, w_depth=1.0, seed=None):
+def tracking_l1(im, depth_sil, gt_im, gt_depth, sil_thres=0.99, w_im=0.5, w_depth=1.0, seed=None, terms=None):
     """w_im * sum(mask*|gt_im - im|) + w_depth * sum(mask*|gt_depth - depth|) with SplaTAM's tracking mask.
 
     seed: optional device scalar that the caller will pass to backward() (a static
     seed, e.g. GraphTracker's ones): the gradient images are then computed in the
     forward pass, from the seed's value at that time; a backward seeded with any
-    other tensor computes them itself."""
-    return _TrackingL1.apply(im, depth_sil, gt_im, gt_depth, sil_thres, w_im, w_depth, seed)
+    other tensor computes them itself.
+    terms: optional device float32 [2]: receives the two weighted terms (w_im * image sum, w_depth * depth
+    sum -- get_loss's losses['im'] / losses['depth']) next to the loss (the _terms entry points)."""
+    return _TrackingL1.apply(im, depth_sil, gt_im, gt_depth, sil_thres, w_im, w_depth, seed, terms)
 
 
 # ------------------------------------------------------------------ mapping --
@@ -507,7 +519,7 @@ class _TrackIteration(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cam_rots, cam_trans, params, curr, t, cfg, pose_adam, capacity, status, means2D, seed,
-                images=True, alive=None):
+                images=True, alive=None, terms=None):
         from . import _C
         cam = curr["cam"]
         cam_rots, cam_trans = _f32c(cam_rots, "cam_unnorm_rots"), _f32c(cam_trans, "cam_trans")
@@ -544,7 +556,8 @@ class _TrackIteration(torch.autograd.Function):
             # taken from another seed, which then raises
             (n, im, ds, radii, geom, binning, img, _, loss, dim, dds) = _C.track_forward_dual_static(
                 cam, means, rgb, dcol, opac, scales, rot, capacity, status, gt_im, gt_d, cfg.sil_thres, cfg.w_im,
-                cfg.w_depth, seed, scratch, xform=xform, records=records, images=images or records is None)
+                cfg.w_depth, seed, scratch, xform=xform, records=records, images=images or records is None,
+                terms=terms)
             ctx.pre = (dim, dds, seed)
             ctx.records = records
             ctx.save_for_backward(cam_rots, cam_trans, mw, ur, means, rot, dcol, scales, rgb, radii, geom, binning,
@@ -567,7 +580,7 @@ class _TrackIteration(torch.autograd.Function):
             scratch = _scratch(mw, lib.gsr_track_forward_scratch_floats(W, H))
             (n, im, ds, radii, geom, binning, img, _, loss, dim, dds) = _C.track_forward_dual_static(
                 cam, means, rgb, dcol, opac, scales, rot, capacity, status, gt_im, gt_d, cfg.sil_thres, cfg.w_im,
-                cfg.w_depth, seed, scratch)
+                cfg.w_depth, seed, scratch, terms=terms)
             ctx.pre = (dim, dds, seed)
             ctx.save_for_backward(cam_rots, cam_trans, mw, ur, means, rot, dcol, scales, rgb, radii, geom, binning,
                                   img, im, ds, gt_im, gt_d, w2c)
@@ -584,19 +597,13 @@ class _TrackIteration(torch.autograd.Function):
             cam.prefiltered, capacity=capacity, status=status)
         loss = torch.empty((), **f32)
         scratch = _scratch(mw, lib.gsr_track_scratch_floats(H * W))
+        dim = dds = None
         if seed is not None:  # static loss seed: the loss gradient images in the same pass
             seed = _f32c(seed, "seed")
             dim, dds = torch.empty_like(im), torch.empty_like(ds)
-            rc = lib.gsr_track_l1_fwd_bwd(H, W, im.data_ptr(), ds.data_ptr(), gt_im.data_ptr(), gt_d.data_ptr(),
-                                          float(cfg.sil_thres), float(cfg.w_im), float(cfg.w_depth), seed.data_ptr(),
-                                          loss.data_ptr(), dim.data_ptr(), dds.data_ptr(), scratch.data_ptr(),
-                                          _stream(mw))
             ctx.pre = (dim, dds, seed)
-        else:
-            rc = lib.gsr_track_l1_fwd(H, W, im.data_ptr(), ds.data_ptr(), gt_im.data_ptr(), gt_d.data_ptr(),
-                                      float(cfg.sil_thres), float(cfg.w_im), float(cfg.w_depth), loss.data_ptr(),
-                                      scratch.data_ptr(), _stream(mw))
-        _check(rc, "track_l1")
+        _track_l1(H, W, im, ds, gt_im, gt_d, cfg.sil_thres, cfg.w_im, cfg.w_depth, seed, loss, terms, dim, dds,
+                  scratch)
         ctx.save_for_backward(cam_rots, cam_trans, mw, ur, means, rot, dcol, scales, rgb, radii, geom, binning, img,
                               im, ds, gt_im, gt_d, w2c)
         ctx.meta = (t, T, scols, int(n), cam, cfg)
@@ -613,7 +620,7 @@ class _TrackIteration(torch.autograd.Function):
         (cam_rots, cam_trans, mw, ur, means, rot, dcol, scales, rgb, radii, geom, binning, img, im, ds, gt_im, gt_d,
          w2c) = ctx.saved_tensors
         t, T, scols, n, cam, cfg = ctx.meta
-        nones = (None,) * 13
+        nones = (None,) * 14
         records = getattr(ctx, "records", None)
         if ctx.pre is not None and g is not None and g.data_ptr() == ctx.pre[2].data_ptr():
             dim, dds = ctx.pre[0], ctx.pre[1]
@@ -649,20 +656,21 @@ class _TrackIteration(torch.autograd.Function):
                                scols, cam_rots.data_ptr() + 4 * t, cam_trans.data_ptr() + 4 * t, T, w2c, scratch,
                                dq_ptr=dq.data_ptr() + 4 * t, dt_ptr=dt.data_ptr() + 4 * t, log_scales=ctx.log_scales,
                                records=records)
-        return (dq, dt) + (None,) * 11
+        return (dq, dt) + (None,) * 12
 
 
 def tracking_iteration(params: dict, curr: dict, time_idx: int, cfg, pose_adam: PoseAdam | None = None,
-                       capacity: int = 0, status=None, seed=None, images: bool = True, alive=None):
+                       capacity: int = 0, status=None, seed=None, images: bool = True, alive=None, terms=None):
     """get_loss(tracking=True) as one fused forward (transform, dual rasterization, masked L1) whose backward
     runs the render backward and the per-Gaussian backward with the pose chain (+ pose Adam) fused in:
     no per-Gaussian gradient array, no separate pose-reduction launch.  Returns (loss, radii).
     images=False: with the render backward fused into the forward's launch (static mode and seed), the
     rendered images are not stored at all (get_loss reads them only for the loss, formed in the same launch);
     the backward must then be taken from `seed`.  alive (uint8 [P], static form only): the Gaussians with
-    alive[i] == 0 are culled (a capacity-padded map's free and pruned slots)."""
+    alive[i] == 0 are culled (a capacity-padded map's free and pruned slots).  terms (device float32 [2]): the
+    forward also publishes the loss's two weighted terms there (tracking_l1), whichever of its forms runs."""
     return _TrackIteration.apply(params["cam_unnorm_rots"], params["cam_trans"], params, curr, int(time_idx), cfg,
-                                 pose_adam, int(capacity), status, None, seed, bool(images), alive)
+                                 pose_adam, int(capacity), status, None, seed, bool(images), alive, terms)
 
 
 class _DualRenderL1(torch.autograd.Function):
@@ -672,13 +680,13 @@ class _DualRenderL1(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, colors, colors2, opacities, scales, rotations, st, capacity, status, gt_im, gt_depth,
-                cfg, seed):
+                cfg, seed, terms=None):
         from . import _C
         H, W = st.image_height, st.image_width
         scratch = _scratch(means3D, lib.gsr_track_forward_scratch_floats(W, H))
         (n, im, ds, radii, geom, binning, img, _, loss, dim, dds) = _C.track_forward_dual_static(
             st, means3D, colors, colors2, opacities, scales, rotations, capacity, status, gt_im, gt_depth,
-            cfg.sil_thres, cfg.w_im, cfg.w_depth, seed, scratch)
+            cfg.sil_thres, cfg.w_im, cfg.w_depth, seed, scratch, terms=terms)
         ctx.save_for_backward(colors, colors2, means3D, scales, rotations, radii, geom, binning, img, im, ds, gt_im,
                               gt_depth)
         ctx.meta = (st, int(n), cfg)
@@ -693,7 +701,7 @@ class _DualRenderL1(torch.autograd.Function):
         colors, colors2, means3D, scales, rotations, radii, geom, binning, img, im, ds, gt_im, gt_d = ctx.saved_tensors
         st, n, cfg = ctx.meta
         if g is None:
-            return (None,) * 13
+            return (None,) * 14
         if g.data_ptr() == ctx.pre[2].data_ptr():
             dim, dds = ctx.pre[0], ctx.pre[1]
         else:
@@ -710,12 +718,13 @@ class _DualRenderL1(torch.autograd.Function):
             st.bg, means3D, radii, colors, colors2, scales, rotations, st.scale_modifier, empty, st.viewmatrix,
             st.projmatrix, st.tanfovx, st.tanfovy, dim, dds, empty, st.sh_degree, st.campos, geom, n, binning, img,
             needs=needs, dl2_channels=1)
-        return (g_m3 if nd[0] else None, g_col, g_col2, g_op, g_sc, g_rot) + (None,) * 7
+        return (g_m3 if nd[0] else None, g_col, g_col2, g_op, g_sc, g_rot) + (None,) * 8
 
 
 def dual_render_tracking_l1(means3D, colors, colors2, opacities, scales, rotations, raster_settings, capacity, status,
-                            gt_im, gt_depth, cfg, seed):
+                            gt_im, gt_depth, cfg, seed, terms=None):
     """(loss, radii) of the tracking iteration's two renders + L1 loss, one static dual rasterization with
-    the loss formed in the render epilogue (HIP-graph capturable; check `status` for overflow)."""
+    the loss formed in the render epilogue (HIP-graph capturable; check `status` for overflow).  terms: as
+    tracking_l1's."""
     return _DualRenderL1.apply(means3D, colors, colors2, opacities, scales, rotations, raster_settings, int(capacity),
-                               status, gt_im, gt_depth, cfg, seed)
+                               status, gt_im, gt_depth, cfg, seed, terms)

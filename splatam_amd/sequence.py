@@ -36,10 +36,18 @@ Two keyframe policies (`keyframe_policy`):
   densification and before mapping) from a KeyframeBank that is appended at frame 0, at every
   keyframe_every-th frame and at frame num_frames - 2 (:932) with the pose as estimated then; the mapper
   gathers its per-iteration keyframes from the device-resident draws (GraphMapper.run(device_sequence=...)),
-  so frame() still reads nothing back.  Randomness comes as 32-bit words from the sequence's numpy stream
+  so frame() still reads nothing back (but see track_cfg.use_depth_loss_thres below).  Randomness comes as 32-bit words from the sequence's numpy stream
   (`draws` records them); PerFrameSlam runs keyframes.select_literal on the same words.  The two deliberate
   differences from the reference (the random-word mapping, distinct pixels in one 1e-4 m cell are kept) are
   stated in splatam_amd/keyframes.py and include/gsr_glue.h.
+
+track_cfg.use_depth_loss_thres (the reference's iPhone and ScanNet++ configurations; scripts/splatam.py:745-758):
+a frame whose last tracking iteration's depth loss is not below track_cfg.depth_loss_thres tracks for
+tracking_iters more iterations, once.  Both loops then build their trackers with loss_terms=True and pass the
+threshold to GraphTracker.track_frame, which reads that one float per tracked frame -- the only host read of
+frame(), and only with the option on (the reference reads the loss in every iteration).  tracking_iters_run
+lists, per frame() call, the tracking iterations run (0 for frame 0, which is not tracked): an entry of
+2 * tracking_iters is one of the reference's "Extra Tracking Iters Frames".
 """
 from __future__ import annotations
 
@@ -264,6 +272,12 @@ class _SequenceBase:
         if self.scene_radius is None:  # initialize_first_timestep: max depth / scene_radius_depth_ratio (3, the config's)
             self.scene_radius = self.frames[0]["depth"].max() / 3.0
         self.keyframes = [self._kf(0)]
+        self.tracking_iters_run = []  # per frame() call: the tracking iterations run (0: frame 0, not tracked)
+
+    def _depth_loss_thres(self):
+        """GraphTracker.track_frame's depth_loss_thres: the configured threshold, or None (option off)."""
+        cfg = self.track_cfg
+        return float(cfg.depth_loss_thres) if cfg.use_depth_loss_thres else None
 
     def _kf(self, t: int) -> dict:
         return {"cam": self.cam, "w2c": self.w2c, "im": self.frames[t]["im"], "depth": self.frames[t]["depth"], "id": t}
@@ -347,7 +361,7 @@ class SlamSequence(_SequenceBase):
         self.slot_curr = {"cam": self.cam, "w2c": self.w2c, "im": f0["im"].clone(), "depth": f0["depth"].clone()}
         self.tracker = GraphTracker(self.slot, self.slot_curr, 0, iters_per_graph=self.track_replay,
                                     cfg=self.track_cfg, warmup_iters=1, fuse_pose=True, alive=self.alive,
-                                    capacity=self.bin_capacity)
+                                    capacity=self.bin_capacity, loss_terms=self.track_cfg.use_depth_loss_thres)
         self.mapper = GraphMapper(self.params, self.keyframes, iters_per_graph=self.mapping_iters, cfg=self.map_cfg,
                                   seed=self.seed, prune=self.prune, scene_radius=self.scene_radius,
                                   alive=self.alive, capacity=self.bin_capacity)
@@ -368,7 +382,8 @@ class SlamSequence(_SequenceBase):
 
     def track(self, t: int):
         """initialize_camera_pose, then tracking_iters iterations from the pose slot (best candidate written
-        back into column t)."""
+        back into column t); with track_cfg.use_depth_loss_thres, once more unless the depth loss fell below the
+        threshold (one host read).  Returns the iterations run."""
         p = self.params
         initialize_camera_pose(p, t)
         with torch.no_grad():
@@ -376,10 +391,11 @@ class SlamSequence(_SequenceBase):
             self.slot["cam_trans"][..., 0] = p["cam_trans"][..., t]
             self.slot_curr["im"].copy_(self.frames[t]["im"])
             self.slot_curr["depth"].copy_(self.frames[t]["depth"])
-        self.tracker.track_frame(self.tracking_iters, check=False)
+        ran = self.tracker.track_frame(self.tracking_iters, check=False, depth_loss_thres=self._depth_loss_thres())
         with torch.no_grad():
             p["cam_unnorm_rots"][..., t] = self.slot["cam_unnorm_rots"][..., 0]
             p["cam_trans"][..., t] = self.slot["cam_trans"][..., 0]
+        return ran
 
     def densify(self, t: int):
         """add_new_gaussians without a host read.  densify_mode "torch": densify_static; "device": the
@@ -438,9 +454,11 @@ class SlamSequence(_SequenceBase):
 
     def frame(self, t: int, sequence=None):
         """One frame of scripts/splatam.py:697-929: tracking (t > 0), densification (t > 0), mapping."""
+        ran = 0
         if t > 0:
-            self.track(t)
+            ran = self.track(t)
             self.densify(t)
+        self.tracking_iters_run.append(ran)
         self.map(t, sequence)
 
     def check(self):
@@ -500,20 +518,24 @@ class PerFrameSlam(_SequenceBase):
 
     def frame(self, t: int, sequence):
         p = self.p
+        ran = 0
         if t > 0:
             initialize_camera_pose(p, t)
             tp = dict(p)
             tp["cam_unnorm_rots"] = p["cam_unnorm_rots"][..., t:t + 1].clone().requires_grad_(True)
             tp["cam_trans"] = p["cam_trans"][..., t:t + 1].clone().requires_grad_(True)
             curr = {"cam": self.cam, "w2c": self.w2c, "im": self.frames[t]["im"], "depth": self.frames[t]["depth"]}
-            GraphTracker(tp, curr, 0, iters_per_graph=self.track_replay, cfg=self.track_cfg, warmup_iters=1,
-                         fuse_pose=True, capacity=self.bin_capacity).track_frame(self.tracking_iters)
+            tracker = GraphTracker(tp, curr, 0, iters_per_graph=self.track_replay, cfg=self.track_cfg, warmup_iters=1,
+                                   fuse_pose=True, capacity=self.bin_capacity,
+                                   loss_terms=self.track_cfg.use_depth_loss_thres)
+            ran = tracker.track_frame(self.tracking_iters, depth_loss_thres=self._depth_loss_thres())
             with torch.no_grad():
                 p["cam_unnorm_rots"][..., t] = tp["cam_unnorm_rots"][..., 0]
                 p["cam_trans"][..., t] = tp["cam_trans"][..., 0]
             kf, intr = self._densify_kf(t)
             add = add_new_gaussians_device if self.densify_mode == "device" else add_new_gaussians_literal
             p = add(p, kf, t, intr, self.sil_thres)
+        self.tracking_iters_run.append(ran)
         mp = {k: (v.detach().requires_grad_(True) if k in GAUSS_KEYS + ("rgb_colors",) else v) for k, v in p.items()}
         if self.keyframe_policy == "overlap":
             win, sequence = self._select_overlap(p, t, sequence)

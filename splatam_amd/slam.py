@@ -123,6 +123,11 @@ class TrackingConfig:
     ignore_outlier_depth_loss: bool = False
     w_im: float = 0.5
     w_depth: float = 1.0
+    # scripts/splatam.py:464-466 (the defaults) and :745-758: a frame whose last iteration's depth loss is not
+    # below depth_loss_thres gets its tracking iterations once more (on in configs/iphone/* and
+    # configs/scannetpp/*; off for Replica and TUM).  Read by the loops (sequence.py) and track_frame_literal.
+    use_depth_loss_thres: bool = False
+    depth_loss_thres: float = 100000.0
 
 
 def fused_eligible(params, curr_data, cfg: TrackingConfig) -> bool:
@@ -135,9 +140,10 @@ def fused_eligible(params, curr_data, cfg: TrackingConfig) -> bool:
 
 
 def _get_loss_tracking_fused(params, curr_data, iter_time_idx, cfg: TrackingConfig, dual=True, capacity=0,
-                             status=None, pose_adam=None, means2D=None, seed=None):
+                             status=None, pose_adam=None, means2D=None, seed=None, terms=None):
     """means2D: optional caller-owned [P,3] tensor (the tracker passes a static one without grad).
-    seed: the static loss seed the caller will backward with (loss gradient formed in the forward)."""
+    seed: the static loss seed the caller will backward with (loss gradient formed in the forward).
+    terms: optional device float32 [2] receiving the loss's two weighted terms (glue.tracking_l1)."""
     from .glue import dual_render_tracking_l1, track_transform, tracking_l1
     means, rots, dcol, opac, scales = track_transform(params, iter_time_idx, curr_data["w2c"], pose_adam)
     P = means.shape[0]
@@ -145,7 +151,8 @@ def _get_loss_tracking_fused(params, curr_data, iter_time_idx, cfg: TrackingConf
         means2D = torch.zeros(P, 3, device=means.device, requires_grad=True)
     if dual and capacity > 0 and seed is not None:  # static mode with a static seed: loss in the render epilogue
         loss, radius = dual_render_tracking_l1(means, params["rgb_colors"], dcol, opac, scales, rots, curr_data["cam"],
-                                               capacity, status, curr_data["im"], curr_data["depth"], cfg, seed)
+                                               capacity, status, curr_data["im"], curr_data["depth"], cfg, seed,
+                                               terms=terms)
         return loss, radius, means2D
     if dual:  # both renders in one rasterization (means2D.grad then holds the sum over both images)
         im, depth_sil, radius, _ = rasterize_gaussians_dual(means, means2D, None, params["rgb_colors"], dcol, opac,
@@ -159,12 +166,12 @@ def _get_loss_tracking_fused(params, curr_data, iter_time_idx, cfg: TrackingConf
         depth_sil, _, _ = ras(means3D=means, means2D=means2D_ds, colors_precomp=dcol, opacities=opac, scales=scales,
                               rotations=rots)
     loss = tracking_l1(im, depth_sil, curr_data["im"], curr_data["depth"], cfg.sil_thres, cfg.w_im, cfg.w_depth,
-                       seed=seed)
+                       seed=seed, terms=terms)
     return loss, radius, means2D
 
 
 def get_loss_tracking(params, curr_data, iter_time_idx, cfg: TrackingConfig = TrackingConfig(), fast=True,
-                      fused=True, dual=True, fuse_pose=False, variables=None, renderer=None):
+                      fused=True, dual=True, fuse_pose=False, variables=None, renderer=None, losses_out=None):
     """scripts/splatam.py:220-353 with tracking=True: two renders (RGB, [z,1,z^2]), masked L1 sums.
 
     fused=True (and fused_eligible): the pose transform / rendervar builders and
@@ -177,8 +184,12 @@ def get_loss_tracking(params, curr_data, iter_time_idx, cfg: TrackingConfig = Tr
     literal statement of the reference code.  fuse_pose=True (with fused, dual): one autograd node for the
     whole iteration whose backward fuses the pose chain into the rasterizer's per-Gaussian backward
     (glue.tracking_iteration, gsr_track_backward_dual).  variables: SplaTAM's densification statistics,
-    updated like splatam.py:257,349-351 (literal path only)."""
+    updated like splatam.py:257,349-351 (literal path only).  losses_out (a dict, eager paths only): receives
+    the reference's weighted_losses (:345-351): "im" = w_im * loss_im, "depth" = w_depth * loss_depth, "loss"."""
     if fused and fast and fused_eligible(params, curr_data, cfg):
+        if losses_out is not None:
+            raise RuntimeError("get_loss_tracking: losses_out is the eager paths' (fused=False); the fused "
+                               "forwards publish their terms on the device (glue.tracking_l1(terms=...))")
         if fuse_pose and dual:
             from .glue import tracking_iteration
             loss, radius = tracking_iteration(params, curr_data, iter_time_idx, cfg)
@@ -210,6 +221,8 @@ def get_loss_tracking(params, curr_data, iter_time_idx, cfg: TrackingConfig = Tr
         loss_depth = torch.abs(curr_data["depth"] - depth)[mask].sum()
         loss_im = torch.abs(curr_data["im"] - im)[color_mask].sum()
     loss = cfg.w_im * loss_im + cfg.w_depth * loss_depth
+    if losses_out is not None:
+        losses_out.update(im=cfg.w_im * loss_im, depth=cfg.w_depth * loss_depth, loss=loss)
     if variables is not None:  # splatam.py:257,349-351
         variables["means2D"] = rendervar["means2D"]
         seen = radius > 0
@@ -486,21 +499,28 @@ def tracking_optimizer(params: dict, lrs: dict = TRACKING_LRS):
 
 
 def track_frame_literal(params, variables, curr_data, time_idx, num_iters, cfg: TrackingConfig = TrackingConfig(),
-                        optimizer=None, losses_out=None, renderer=None):
-    """The unchanged tracking loop body of scripts/splatam.py:700-763 for one frame (use_gt_poses=False,
-    no depth-loss-threshold extension): get_loss(tracking=True) through two GaussianRasterizer calls,
+                        optimizer=None, losses_out=None, renderer=None, iters_out=None):
+    """The unchanged tracking loop body of scripts/splatam.py:700-763 for one frame (use_gt_poses=False):
+    get_loss(tracking=True) through two GaussianRasterizer calls,
     loss.backward(), Adam over every parameter group, zero_grad, the best-candidate pose kept by loss
     (:726-731) and written back after the last iteration (:760-763).  renderer: the GaussianRasterizer class
     the caller imports (default splatam_amd's; diff_gaussian_rasterization's is the same drop-in).
+    cfg.use_depth_loss_thres: the reference's `while True` loop (:706-758) as it stands -- at iteration
+    num_iters, losses['depth'] (the weighted depth term) below cfg.depth_loss_thres ends the frame, otherwise
+    the count doubles, once.  iters_out (a list): the number of iterations run is appended.
     Returns the optimizer."""
     if optimizer is None:
         optimizer = tracking_optimizer(params)
     cand_rot = params["cam_unnorm_rots"][..., time_idx].detach().clone()
     cand_tran = params["cam_trans"][..., time_idx].detach().clone()
     current_min_loss = float(1e20)
-    for _ in range(num_iters):
+    it = 0
+    do_continue_slam = False
+    num_iters_tracking = num_iters
+    losses = {} if cfg.use_depth_loss_thres else None  # (the weighted terms are formed only when they are read)
+    while True:
         loss, _radius, _m2d = get_loss_tracking(params, curr_data, time_idx, cfg, fast=False, fused=False,
-                                                variables=variables, renderer=renderer)
+                                                variables=variables, renderer=renderer, losses_out=losses)
         loss.backward()
         optimizer.step()
         optimizer.zero_grad(set_to_none=True)
@@ -511,6 +531,17 @@ def track_frame_literal(params, variables, curr_data, time_idx, num_iters, cfg: 
                 current_min_loss = loss
                 cand_rot = params["cam_unnorm_rots"][..., time_idx].detach().clone()
                 cand_tran = params["cam_trans"][..., time_idx].detach().clone()
+        it += 1
+        if it == num_iters_tracking:  # :747-758
+            if cfg.use_depth_loss_thres and losses["depth"] < cfg.depth_loss_thres:
+                break
+            elif cfg.use_depth_loss_thres and not do_continue_slam:
+                do_continue_slam = True
+                num_iters_tracking = 2 * num_iters_tracking
+            else:
+                break
+    if iters_out is not None:
+        iters_out.append(it)
     with torch.no_grad():
         params["cam_unnorm_rots"][..., time_idx] = cand_rot
         params["cam_trans"][..., time_idx] = cand_tran

@@ -27,6 +27,14 @@ pose after the step of the lowest-loss iteration (:726-731, :760-763), tracked
 on the device inside the captured backward.  `track_frame(num_iters)` does all
 three.  The warm-up iterations run at construction are undone (pose restored,
 optimizer reset).
+
+The reference's use_depth_loss_thres (scripts/splatam.py:745-758; on in its iPhone and ScanNet++
+configurations): when the depth loss of the frame's last iteration is not below depth_loss_thres, the
+frame gets num_iters more iterations, once.  A tracker built with loss_terms=True has every captured
+iteration publish the loss's two weighted terms into its row of `terms` (the _terms entry points of
+include/gsr_glue.h), and track_frame(..., depth_loss_thres=...) reads terms[iters - 1, 1] -- one float, one
+host read per frame -- between the two halves.  The reference reads the loss on the host in every iteration;
+the default (no threshold) still reads nothing.
 """
 from __future__ import annotations
 
@@ -38,6 +46,26 @@ from .rasterizer import GaussianRasterizationSettings
 from .slam import TrackingConfig, _get_loss_tracking_fused, fused_eligible
 
 TILE_SORT_CAP = 4096  # longest tile list the static mode handles (render_fwd's per-tile sort)
+
+
+def run_frame(tracker, num_iters: int, depth_loss_thres: float | None = None) -> int:
+    """One frame's replays on `tracker` (begin_frame(), run() = `iters` iterations, end_frame(), and with a
+    threshold `terms`, the [iters, 2] tensor of the last replay's loss terms): the reference's tracking loop
+    with use_depth_loss_thres (scripts/splatam.py:706-758).  num_iters iterations; then, with a threshold, the
+    depth term of the last one is read (the frame's one host read) and unless it is < depth_loss_thres
+    (`if depth < thres: break / elif not continued: extend`, so a NaN extends) num_iters more follow -- once
+    (do_continue_slam): the optimizer state and the best candidate carry on.  Returns the iterations run."""
+    replays = num_iters // tracker.iters
+    tracker.begin_frame()
+    for _ in range(replays):
+        tracker.run()
+    ran = num_iters
+    if depth_loss_thres is not None and not float(tracker.terms[tracker.iters - 1, 1]) < depth_loss_thres:
+        for _ in range(replays):
+            tracker.run()
+        ran += num_iters
+    tracker.end_frame()
+    return ran
 
 
 def probe_num_rendered(params, curr_data, time_idx) -> tuple[int, int]:
@@ -61,7 +89,7 @@ class GraphTracker:
                  cfg: TrackingConfig = TrackingConfig(), lrs=(0.0004, 0.002), headroom: float = 1.5,
                  warmup_iters: int = 3, min_extra: int = 65536, timing: bool = False, fuse_pose: bool = False,
                  prime: bool = False, prime_ms: float = 0.0, clock_stages=None, alive=None,
-                 capacity: int | None = None):
+                 capacity: int | None = None, loss_terms: bool = False):
         if not fused_eligible(params, curr_data, cfg):
             raise RuntimeError("GraphTracker needs the fused tracking configuration (only the pose requires grad)")
         self.params, self.curr, self.t, self.cfg = params, curr_data, time_idx, cfg
@@ -79,6 +107,9 @@ class GraphTracker:
         self.capacity = int(capacity)
         self.iters = int(iters_per_graph)
         self.status = torch.zeros(self.iters, 4, dtype=torch.int32, device=dev)
+        # loss_terms: captured iteration k also publishes (w_im * image sum, w_depth * depth sum) into terms[k]
+        # (the forwards' _terms entry points); False captures today's graph with today's entry points
+        self.terms = torch.zeros(self.iters, 2, dtype=torch.float32, device=dev) if loss_terms else None
         rots, trans = params["cam_unnorm_rots"], params["cam_trans"]
         if not (rots.is_leaf and trans.is_leaf and rots.requires_grad and trans.requires_grad):
             raise RuntimeError("cam_unnorm_rots / cam_trans must be leaf tensors requiring grad")
@@ -138,18 +169,19 @@ class GraphTracker:
 
     def _iteration(self, k: int):
         self.adam.status = self.status[k]  # this iteration's forward guards its Adam step
+        terms = self.terms[k] if self.terms is not None else None
         if self.fuse_pose:
             from .glue import tracking_iteration
             # (images=False: the replays keep the rendered images in registers -- the loss and the render
             # backward run in the same launch and the tracker reads neither image)
             loss, _ = tracking_iteration(self.params, self.curr, self.t, self.cfg, pose_adam=self.adam,
                                          capacity=self.capacity, status=self.status[k], seed=self.seed,
-                                         images=False, alive=self.alive)
+                                         images=False, alive=self.alive, terms=terms)
             torch.autograd.backward(loss, self.seed)
             return loss.detach()
         loss, _, _ = _get_loss_tracking_fused(self.params, self.curr, self.t, self.cfg, dual=True,
                                               capacity=self.capacity, status=self.status[k], pose_adam=self.adam,
-                                              means2D=self.means2D, seed=self.seed)
+                                              means2D=self.means2D, seed=self.seed, terms=terms)
         self.adam.loss = loss  # best-candidate selection in the transform backward
         torch.autograd.backward(loss, self.seed)
         self.adam.loss = None
@@ -169,8 +201,15 @@ class GraphTracker:
             self.params["cam_unnorm_rots"][0, :, self.t] = self.adam.best[1:5]
             self.params["cam_trans"][0, :, self.t] = self.adam.best[5:8]
 
-    def track_frame(self, num_iters: int, check: bool = True):
+    def track_frame(self, num_iters: int, check: bool = True, depth_loss_thres: float | None = None) -> int:
         """One frame's tracking: begin_frame, num_iters iterations (a multiple of iters_per_graph), end_frame.
+        Returns the number of iterations run.
+
+        depth_loss_thres (the reference's use_depth_loss_thres / depth_loss_thres, needs loss_terms=True): after
+        the num_iters iterations the last one's depth term w_depth * sum(mask |gt_depth - depth|) is read -- one
+        float, the frame's one host read; the reference reads its loss in every iteration -- and unless it is
+        below the threshold (a NaN is not) the frame runs num_iters more, once (run_frame).  None: nothing is
+        read beyond `check`'s.
 
         An iteration whose forward overflowed skips its own pose step (the fused steps guard on that
         forward's counters, not on the sticky status rows; the pose optimizer's step count lives on the
@@ -179,15 +218,17 @@ class GraphTracker:
         check=False (timing loops) skips the sync: read overflowed() afterwards."""
         if num_iters % self.iters:
             raise ValueError(f"num_iters {num_iters} is not a multiple of iters_per_graph {self.iters}")
+        if depth_loss_thres is not None and self.terms is None:
+            raise RuntimeError("track_frame(depth_loss_thres=...) needs a tracker built with loss_terms=True")
         if check:
             self.reset_status()
-        self.begin_frame()
-        for _ in range(num_iters // self.iters):
-            self.run()
-        self.end_frame()
+        ran = run_frame(self, num_iters, depth_loss_thres)
+        # (an overflowed iteration's terms are as invalid as its loss: with `check` the frame raises here whatever
+        # they decided; with check=False the caller reads overflowed() as before)
         if check and self.overflowed():
             raise RuntimeError(f"binning capacity {self.capacity} exceeded while tracking frame {self.t}: "
                                "rebuild the tracker with more headroom and re-run the frame")
+        return ran
 
     def reset_status(self):
         self.status.zero_()
