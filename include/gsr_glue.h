@@ -596,6 +596,38 @@ int gsr_densify_frame(int H, int W, const float* depth_sil, const float* gt_im, 
                       unsigned char* alive, long long* n_live, unsigned char* overflow, long long* n_added, int* dest,
                       void* workspace, void* stream);
 
+/* gsr_densify_frame with the realtime loop's threshold (add_new_gaussians of scripts/splatam_realtime.py:
+ * 430-482, its median_thr and median_scale): the contract above word for word, the same six launches and
+ * the same workspace, except step 3's thr:
+ *   use_median_thr != 0 and med > median_thr (false for a NaN med):
+ *                             thr = (float)((double)median_scale * (double)median_thr) -- the product the
+ *                             reference forms from two Python floats before torch rounds it to float32;
+ *   use_median_thr != 0 otherwise: thr = 50.f * med.  median_scale is NOT used here: the reference resets
+ *                             its scale to 50 on this branch (:450-451), and that quirk is kept;
+ *   use_median_thr == 0:      thr = median_scale * med, in float32.
+ * use_median_thr is the reference's `median_thr is not None`.  gsr_densify_frame is this call with
+ * (0, 0, 50.f).  The decision is made in the kernel that reads med (no launch of its own).  The three
+ * arguments come last.  Errors name "densify_frame_capped". */
+int gsr_densify_frame_capped(int H, int W, const float* depth_sil, const float* gt_im, const float* gt_depth,
+                             float fx, float fy, float cx, float cy, const float* w2c, float sil_thres, int capacity,
+                             float* means3D, float* rgb_colors, float* unnorm_rotations, float* logit_opacities,
+                             float* log_scales, unsigned char* alive, long long* n_live, unsigned char* overflow,
+                             long long* n_added, int* dest, void* workspace, void* stream, int use_median_thr,
+                             float median_thr, float median_scale);
+
+/* initialize_first_timestep's point cloud (scripts/splatam_realtime.py:229-237) on a capacity-padded map:
+ * selected = gt > 0 for every pixel -- no silhouette render is read and no median is formed -- and then
+ * steps 4-6 of gsr_densify_frame exactly (rows n_live + rank in row-major order, the same values, n_added,
+ * n_live, overflow, dest), by the same two kernels: two launches.  w2c: the first frame's world-to-camera
+ * matrix.  A map that starts empty passes n_live = 0 and an all-zero alive.
+ * workspace: gsr_densify_workspace_bytes(H, W) bytes under the contract above; the call uses one of the
+ * four arrival counters and leaves it zero, so one buffer serves any interleaving of the three entries on
+ * one stream.  Refuses what gsr_densify_frame refuses (there is no depth_sil); errors name "init_frame". */
+int gsr_init_frame(int H, int W, const float* gt_im, const float* gt_depth, float fx, float fy, float cx, float cy,
+                   const float* w2c, int capacity, float* means3D, float* rgb_colors, float* unnorm_rotations,
+                   float* logit_opacities, float* log_scales, unsigned char* alive, long long* n_live,
+                   unsigned char* overflow, long long* n_added, int* dest, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

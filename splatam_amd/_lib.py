@@ -211,6 +211,14 @@ SIGNATURES = {
     "gsr_densify_frame": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                   c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # (gsr_densify_frame's arguments, then use_median_thr, median_thr, median_scale)
+    "gsr_densify_frame_capped": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float,
+                                         c_float, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_int, c_float, c_float]),
+    "gsr_init_frame": (c_int, [c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_int,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -15,6 +15,12 @@
 //   dn_scatter_kernel   row = old n_live + workgroup prefix + the popcount rank inside the workgroup;
 //                       the selected pixels' Gaussians, alive, dest.
 //
+// gsr_densify_frame_capped is the same six launches with the realtime loop's threshold
+// (median_thr / median_scale, scripts/splatam_realtime.py:444-453), decided where dn_count_kernel
+// already reads the median.  gsr_init_frame (initialize_first_timestep's point cloud, :229-237) is the
+// last two launches alone: dn_count_kernel<true> selects every pixel with a measured depth and reads
+// neither depth_sil nor the median, dn_scatter_kernel is the same kernel.
+//
 // Latency-bound work (640x480: 307 k pixels, 150 workgroups of 2048 pixels): the aim is few launches
 // and no wasted bytes -- err is recomputed from the two depth images in every pass (2.4 MB, cache
 // resident) rather than stored, only selected pixels write anything but dest.  All counts are
@@ -165,9 +171,24 @@ __device__ __forceinline__ bool dn_selected(float sil, float rd, float gt, float
     return ((sil < sil_thres) || ((rd > gt) && (err > thr))) && valid;
 }
 
+// Step 3's threshold from the median (include/gsr_glue.h: gsr_densify_frame_capped).  capped: the host's
+// (float)((double)median_scale * (double)median_thr).  A NaN med fails the comparison and stays a NaN.
+struct DnThr {
+    int use_median_thr;
+    float median_thr, median_scale, capped;
+};
+__device__ __forceinline__ float dn_threshold(const DnThr& t, float med) {
+#pragma clang fp contract(off)
+    if (!t.use_median_thr) return t.median_scale * med;
+    return med > t.median_thr ? t.capped : 50.f * med;
+}
+
+// INIT (gsr_init_frame): every pixel with a measured depth is selected; depth_sil, the median and the
+// threshold are not read.
+template <bool INIT>
 __global__ void __launch_bounds__(DN_BLOCK)
 dn_count_kernel(int N, const float* __restrict__ depth_sil, const float* __restrict__ gt_depth, float sil_thres,
-                int capacity, uint32_t* __restrict__ ws, long long* __restrict__ n_live,
+                DnThr tcfg, int capacity, uint32_t* __restrict__ ws, long long* __restrict__ n_live,
                 unsigned char* __restrict__ overflow, long long* __restrict__ n_added) {
 #pragma clang fp contract(off)
     __shared__ uint32_t s_wave[DN_WAVES];
@@ -177,14 +198,17 @@ dn_count_kernel(int N, const float* __restrict__ depth_sil, const float* __restr
     uint32_t* const cnt = ws + lay.cnt;
     uint32_t* const excl = ws + lay.excl;
     unsigned long long* const mask = (unsigned long long*)(ws + lay.mask) + (size_t)blockIdx.x * DN_CHUNKS;
-    const float med = __uint_as_float(ws[DN_NAN] != 0u ? DN_QNAN : ws[DN_MED]);
-    const float thr = 50.f * med;
+    float thr = 0.f;
+    if (!INIT) thr = dn_threshold(tcfg, __uint_as_float(ws[DN_NAN] != 0u ? DN_QNAN : ws[DN_MED]));
     const size_t p0 = (size_t)blockIdx.x * DN_TILE;
     uint32_t count = 0;  // (wave-uniform: every lane adds the wave's popcount)
 #pragma unroll
     for (int i = 0; i < DN_ITEMS; i++) {
         const size_t p = p0 + (size_t)i * DN_BLOCK + tid;
-        const bool sel = p < (size_t)N && dn_selected(depth_sil[(size_t)N + p], depth_sil[p], gt_depth[p], sil_thres, thr);
+        bool sel = false;
+        if (p < (size_t)N)
+            sel = INIT ? gt_depth[p] > 0.f
+                       : dn_selected(depth_sil[(size_t)N + p], depth_sil[p], gt_depth[p], sil_thres, thr);
         const unsigned long long m = __ballot(sel);
         if (lane == 0) mask[i * DN_WAVES + wave] = m;
         count += (uint32_t)__popcll(m);
@@ -264,6 +288,41 @@ dn_scatter_kernel(int H, int W, const float* __restrict__ gt_im, const float* __
 
 using namespace gsr;
 
+// What the three entries share: the argument checks (`who` names the entry in gsr_last_error()), then the
+// count and scatter launches; !INIT: the histogram zeroing and the three selection passes before them.
+template <bool INIT>
+static int dn_enqueue(const char* who, int H, int W, const float* depth_sil, const float* gt_im,
+                      const float* gt_depth, float fx, float fy, float cx, float cy, const float* w2c, float sil_thres,
+                      DnThr tcfg, int capacity, float* means3D, float* rgb_colors, float* unnorm_rotations,
+                      float* logit_opacities, float* log_scales, unsigned char* alive, long long* n_live,
+                      unsigned char* overflow, long long* n_added, int* dest, void* workspace, void* stream) {
+    auto refuse = [&](const char* what) { return fail(GSR_ERR_INVALID_ARG, std::string(who) + ": " + what); };
+    if (!image_size_ok(H, W)) return refuse("bad image size");
+    if (capacity < 0) return refuse("negative capacity");
+    if ((!INIT && !depth_sil) || !gt_im || !gt_depth || !w2c || !means3D || !rgb_colors || !unnorm_rotations ||
+        !logit_opacities || !log_scales || !alive || !n_live || !overflow || !n_added || !workspace)
+        return refuse("null pointer");
+    if (!aligned16(workspace)) return refuse("workspace must be 16-byte aligned");
+    const int N = H * W;
+    const DnLayout lay = DnLayout::make(N);
+    uint32_t* const ws = (uint32_t*)workspace;
+    const DnCam cam{fx, fy, cx, cy, (float)(((double)fx + (double)fy) / 2.0)};
+    const hipStream_t st = (hipStream_t)stream;
+    if (!INIT) {
+        hipLaunchKernelGGL(dn_zero_kernel, dim3(3 * DN_BINS / DN_BLOCK), dim3(DN_BLOCK), 0, st, ws + lay.hist);
+        for (int pass = 0; pass < 3; pass++)
+            hipLaunchKernelGGL(dn_select_kernel, dim3(lay.nb), dim3(DN_BLOCK), 0, st, pass, N, depth_sil, gt_depth,
+                               ws);
+    }
+    hipLaunchKernelGGL(dn_count_kernel<INIT>, dim3(lay.nb), dim3(DN_BLOCK), 0, st, N, depth_sil, gt_depth, sil_thres,
+                       tcfg, capacity, ws, n_live, overflow, n_added);
+    hipLaunchKernelGGL(dn_scatter_kernel, dim3(lay.nb), dim3(DN_BLOCK), 0, st, H, W, gt_im, gt_depth, cam, w2c,
+                       capacity, (const uint32_t*)ws, means3D, rgb_colors, unnorm_rotations, logit_opacities,
+                       log_scales, alive, dest);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GSR_OK : hip_fail(e, who);
+}
+
 extern "C" {
 
 size_t gsr_densify_workspace_bytes(int H, int W) {
@@ -276,27 +335,31 @@ int gsr_densify_frame(int H, int W, const float* depth_sil, const float* gt_im, 
                       float* rgb_colors, float* unnorm_rotations, float* logit_opacities, float* log_scales,
                       unsigned char* alive, long long* n_live, unsigned char* overflow, long long* n_added, int* dest,
                       void* workspace, void* stream) {
-    if (!image_size_ok(H, W)) return fail(GSR_ERR_INVALID_ARG, "densify_frame: bad image size");
-    if (capacity < 0) return fail(GSR_ERR_INVALID_ARG, "densify_frame: negative capacity");
-    if (!depth_sil || !gt_im || !gt_depth || !w2c || !means3D || !rgb_colors || !unnorm_rotations ||
-        !logit_opacities || !log_scales || !alive || !n_live || !overflow || !n_added || !workspace)
-        return fail(GSR_ERR_INVALID_ARG, "densify_frame: null pointer");
-    if (!aligned16(workspace)) return fail(GSR_ERR_INVALID_ARG, "densify_frame: workspace must be 16-byte aligned");
-    const int N = H * W;
-    const DnLayout lay = DnLayout::make(N);
-    uint32_t* const ws = (uint32_t*)workspace;
-    const DnCam cam{fx, fy, cx, cy, (float)(((double)fx + (double)fy) / 2.0)};
-    const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(dn_zero_kernel, dim3(3 * DN_BINS / DN_BLOCK), dim3(DN_BLOCK), 0, st, ws + lay.hist);
-    for (int pass = 0; pass < 3; pass++)
-        hipLaunchKernelGGL(dn_select_kernel, dim3(lay.nb), dim3(DN_BLOCK), 0, st, pass, N, depth_sil, gt_depth, ws);
-    hipLaunchKernelGGL(dn_count_kernel, dim3(lay.nb), dim3(DN_BLOCK), 0, st, N, depth_sil, gt_depth, sil_thres,
-                       capacity, ws, n_live, overflow, n_added);
-    hipLaunchKernelGGL(dn_scatter_kernel, dim3(lay.nb), dim3(DN_BLOCK), 0, st, H, W, gt_im, gt_depth, cam, w2c,
-                       capacity, (const uint32_t*)ws, means3D, rgb_colors, unnorm_rotations, logit_opacities,
-                       log_scales, alive, dest);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GSR_OK : hip_fail(e, "densify_frame");
+    return dn_enqueue<false>("densify_frame", H, W, depth_sil, gt_im, gt_depth, fx, fy, cx, cy, w2c, sil_thres,
+                             DnThr{0, 0.f, 50.f, 0.f}, capacity, means3D, rgb_colors, unnorm_rotations,
+                             logit_opacities, log_scales, alive, n_live, overflow, n_added, dest, workspace, stream);
+}
+
+int gsr_densify_frame_capped(int H, int W, const float* depth_sil, const float* gt_im, const float* gt_depth,
+                             float fx, float fy, float cx, float cy, const float* w2c, float sil_thres, int capacity,
+                             float* means3D, float* rgb_colors, float* unnorm_rotations, float* logit_opacities,
+                             float* log_scales, unsigned char* alive, long long* n_live, unsigned char* overflow,
+                             long long* n_added, int* dest, void* workspace, void* stream, int use_median_thr,
+                             float median_thr, float median_scale) {
+    const DnThr tcfg{use_median_thr != 0, median_thr, median_scale,
+                     (float)((double)median_scale * (double)median_thr)};
+    return dn_enqueue<false>("densify_frame_capped", H, W, depth_sil, gt_im, gt_depth, fx, fy, cx, cy, w2c,
+                             sil_thres, tcfg, capacity, means3D, rgb_colors, unnorm_rotations, logit_opacities,
+                             log_scales, alive, n_live, overflow, n_added, dest, workspace, stream);
+}
+
+int gsr_init_frame(int H, int W, const float* gt_im, const float* gt_depth, float fx, float fy, float cx, float cy,
+                   const float* w2c, int capacity, float* means3D, float* rgb_colors, float* unnorm_rotations,
+                   float* logit_opacities, float* log_scales, unsigned char* alive, long long* n_live,
+                   unsigned char* overflow, long long* n_added, int* dest, void* workspace, void* stream) {
+    return dn_enqueue<true>("init_frame", H, W, nullptr, gt_im, gt_depth, fx, fy, cx, cy, w2c, 0.f,
+                            DnThr{0, 0.f, 50.f, 0.f}, capacity, means3D, rgb_colors, unnorm_rotations,
+                            logit_opacities, log_scales, alive, n_live, overflow, n_added, dest, workspace, stream);
 }
 
 }  // extern "C"

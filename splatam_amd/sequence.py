@@ -48,6 +48,13 @@ threshold to GraphTracker.track_frame, which reads that one float per tracked fr
 frame(), and only with the option on (the reference reads the loss in every iteration).  tracking_iters_run
 lists, per frame() call, the tracking iterations run (0 for frame 0, which is not tracked): an entry of
 2 * tracking_iters is one of the reference's "Extra Tracking Iters Frames".
+
+The realtime loop (scripts/splatam_realtime.py) is the same sequence fed frame by frame: `num_frames` fixes the
+pose columns while the frame list grows, SlamSequence.push(im, depth, w2c=None) appends a frame and runs it,
+a frame with `w2c` (its pose relative to frame 0, tracking.use_gt_poses, :812-821) is not tracked
+(write_given_pose), `map_every` (:844) maps every that-many-th frame, `median_thr` / `median_scale` are
+add_new_gaussians' threshold there (:444-453; densify.depth_threshold, gsr_densify_frame_capped) and
+SlamSequence(params=None) builds the map from the first frame on the device (init_map_device: gsr_init_frame).
 """
 from __future__ import annotations
 
@@ -55,13 +62,14 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .densify import ROW_KEYS, check_densify_args, densify_device
+from .densify import ROW_KEYS, check_densify_args, default_threshold, densify_device, depth_threshold, \
+    init_frame_device, init_literal
 from .densify import make_workspace as make_densify_workspace
 from .keyframes import KeyframeBank, WordFeed, draw_words, make_workspace, pose_w2c, select_device, \
     select_literal, words_tensor
 from .mapper import GAUSS_KEYS, GraphMapper
-from .slam import MappingConfig, TrackingConfig, build_rotation, color_key, transform_to_frame, \
-    transformed_params2depthplussilhouette
+from .slam import MappingConfig, TrackingConfig, build_rotation, color_key, matrix_to_quaternion, \
+    transform_to_frame, transformed_params2depthplussilhouette
 from .tracker import GraphTracker
 
 # dead rows: finite values (the pose-fused backward forms every row's pose partials, zero for culled rows)
@@ -141,14 +149,63 @@ def frame_pointcloud(params: dict, curr: dict, t: int, intrinsics) -> dict:
                 "log_scales": torch.log(torch.sqrt(mean3_sq_dist))[..., None].contiguous()}
 
 
-def non_presence_mask(depth_sil: torch.Tensor, gt_depth: torch.Tensor, sil_thres: float) -> torch.Tensor:
+def identity_poses(num_frames: int, device) -> dict:
+    """initialize_params' camera tensors: the identity quaternion [1, 4, num_frames] and a zero translation
+    [1, 3, num_frames] in every column (poses relative to frame 0)."""
+    q = torch.zeros(1, 4, int(num_frames), dtype=torch.float32, device=device)
+    q[:, 0] = 1.0
+    return {"cam_unnorm_rots": q, "cam_trans": torch.zeros(1, 3, int(num_frames), dtype=torch.float32, device=device)}
+
+
+def init_map_literal(frame: dict, w2c: torch.Tensor, intrinsics, num_frames: int) -> dict:
+    """initialize_first_timestep's map (scripts/splatam_realtime.py:229-237) in torch ops: frame_pointcloud's
+    rows through the first frame's w2c [4,4] for the pixels with a measured depth, in row-major order, and
+    identity_poses.  The rows are formed as gsr_init_frame's contract states them (densify.init_literal:
+    elementwise float32 ops, the matrix product as left-to-right sums, true divisions), so the kernel forms the
+    same bits on any device (log_scales up to logf).  One host synchronisation (the boolean mask)."""
+    out, _, _ = init_literal(frame, w2c, intrinsics)
+    out.update(identity_poses(num_frames, frame["depth"].device))
+    return out
+
+
+def init_map_device(frame: dict, w2c: torch.Tensor, intrinsics, num_frames: int, capacity: int, overflow=None,
+                    workspace=None) -> tuple[dict, torch.Tensor, torch.Tensor]:
+    """(params, alive, n_live): init_map_literal's map as a capacity-padded one without a host read -- pad_map's
+    dead rows, filled from row 0 by gsr_init_frame (densify.init_frame_device, two launches) -- and
+    identity_poses.  overflow (one byte, device): set when the frame has more measured pixels than capacity."""
+    depth = frame["depth"]
+    dev, H, W = depth.device, int(depth.shape[-2]), int(depth.shape[-1])
+    empty = {k: torch.zeros(0, c, dtype=torch.float32, device=dev) for k, c in zip(ROW_KEYS, (3, 3, 4, 1, 1))}
+    params, alive, n_live = pad_map(empty, int(capacity))
+    params.update(identity_poses(num_frames, dev))
+    overflow = torch.zeros(1, dtype=torch.bool, device=dev) if overflow is None else overflow
+    workspace = make_densify_workspace(H, W, dev) if workspace is None else workspace
+    init_frame_device(params, alive, n_live, overflow, frame, w2c.to(torch.float32).contiguous(), intrinsics,
+                      capacity, workspace)
+    return params, alive, n_live
+
+
+def write_given_pose(params: dict, t: int, w2c: torch.Tensor):
+    """A frame whose pose is known (tracking.use_gt_poses, scripts/splatam_realtime.py:812-821): w2c [4,4], the
+    pose relative to frame 0, into column t -- matrix_to_quaternion of its rotation and its translation.
+    Device tensor ops only."""
+    with torch.no_grad():
+        params["cam_unnorm_rots"][..., t] = matrix_to_quaternion(w2c[:3, :3].unsqueeze(0).detach())
+        params["cam_trans"][..., t] = w2c[:3, 3].detach()
+
+
+def non_presence_mask(depth_sil: torch.Tensor, gt_depth: torch.Tensor, sil_thres: float, median_thr=None,
+                      median_scale: float = 50.0) -> torch.Tensor:
     """add_new_gaussians' pixel selection (scripts/splatam.py:391-410), flattened: silhouette below sil_thres,
-    or rendered depth behind the measured depth by more than 50x the median depth error; valid depth only."""
+    or rendered depth behind the measured depth by more than 50x the median depth error; valid depth only.
+    median_thr / median_scale: the realtime loop's threshold (densify.depth_threshold; no host read)."""
     sil = depth_sil[1]
     gt = gt_depth[0]
     rd = depth_sil[0]
     err = torch.abs(gt - rd) * (gt > 0)
-    m = (sil < sil_thres) | ((rd > gt) & (err > 50 * err.median()))
+    thr = 50 * err.median() if default_threshold(median_thr, median_scale) else \
+        depth_threshold(err.median(), median_thr, median_scale)
+    m = (sil < sil_thres) | ((rd > gt) & (err > thr))
     return (m & (gt > 0)).reshape(-1)
 
 
@@ -169,12 +226,13 @@ def render_depth_sil(params: dict, curr: dict, t: int, alive=None, capacity: int
         return ds
 
 
-def add_new_gaussians_literal(params: dict, curr: dict, t: int, intrinsics, sil_thres: float = 0.5) -> dict:
+def add_new_gaussians_literal(params: dict, curr: dict, t: int, intrinsics, sil_thres: float = 0.5, median_thr=None,
+                              median_scale: float = 50.0) -> dict:
     """add_new_gaussians (scripts/splatam.py:384-426) on an unpadded map: the selected pixels' Gaussians
     appended with torch.cat (the reference's reallocation; one host synchronisation for the selection).
     Returns the new params dict (Gaussian tensors new leaves; the camera tensors as they were)."""
     ds = render_depth_sil(params, curr, t)
-    mask = non_presence_mask(ds, curr["depth"], sil_thres)
+    mask = non_presence_mask(ds, curr["depth"], sil_thres, median_thr, median_scale)
     new = frame_pointcloud(params, curr, t, intrinsics)
     out = dict(params)
     for k, v in new.items():
@@ -182,7 +240,8 @@ def add_new_gaussians_literal(params: dict, curr: dict, t: int, intrinsics, sil_
     return out
 
 
-def add_new_gaussians_device(params: dict, curr: dict, t: int, intrinsics, sil_thres: float = 0.5) -> dict:
+def add_new_gaussians_device(params: dict, curr: dict, t: int, intrinsics, sil_thres: float = 0.5, median_thr=None,
+                             median_scale: float = 50.0) -> dict:
     """add_new_gaussians on an unpadded map through the kernel of the padded one: the unpadded silhouette
     render, gsr_densify_frame (splatam_amd.densify.densify_device) on a throw-away padded copy with room
     for every pixel, and the rows up to n_live sliced out with one host read -- what torch.cat would hold,
@@ -195,7 +254,8 @@ def add_new_gaussians_device(params: dict, curr: dict, t: int, intrinsics, sil_t
         padded, alive, n_live = pad_map({k: params[k] for k in ROW_KEYS}, capacity)
         overflow = torch.zeros(1, dtype=torch.bool, device=dev)
         densify_device(padded, alive, n_live, overflow, curr, pose_w2c(params, t), intrinsics, sil_thres, capacity,
-                       ds.contiguous(), make_densify_workspace(H, W, dev))
+                       ds.contiguous(), make_densify_workspace(H, W, dev), median_thr=median_thr,
+                       median_scale=median_scale)
         n = int(n_live.item())
     out = dict(params)
     for k in ROW_KEYS:
@@ -204,13 +264,14 @@ def add_new_gaussians_device(params: dict, curr: dict, t: int, intrinsics, sil_t
 
 
 def densify_static(params: dict, alive: torch.Tensor, n_live: torch.Tensor, overflow: torch.Tensor, curr: dict,
-                   t: int, intrinsics, sil_thres: float, capacity: int, bin_capacity: int, status):
+                   t: int, intrinsics, sil_thres: float, capacity: int, bin_capacity: int, status, median_thr=None,
+                   median_scale: float = 50.0):
     """add_new_gaussians on a capacity-padded map, without a host synchronisation: the selected pixels'
     Gaussians (frame_pointcloud) land in rows n_live + rank, every other pixel writes to the sink row
     `capacity`; alive marks the new rows, n_live grows (clamped; `overflow` set when the map is full)."""
     ds = render_depth_sil(params, curr, t, alive, bin_capacity, status)
     with torch.no_grad():
-        mask = non_presence_mask(ds, curr["depth"], sil_thres)
+        mask = non_presence_mask(ds, curr["depth"], sil_thres, median_thr, median_scale)
         new = frame_pointcloud(params, curr, t, intrinsics)
         incl = torch.cumsum(mask.to(torch.int64), 0)
         dest = n_live + incl - 1
@@ -258,7 +319,7 @@ class _SequenceBase:
     OPTIONS = ("frames", "cam", "w2c", "intrinsics", "bin_capacity", "tracking_iters", "mapping_iters", "track_replay",
                "window", "keyframe_every", "sil_thres", "track_cfg", "map_cfg", "prune", "scene_radius",
                "keyframe_policy", "overlap_pixels", "densify_mode", "densify_frames", "densify_cam",
-               "densify_intrinsics")
+               "densify_intrinsics", "median_thr", "median_scale", "num_frames", "map_every")
 
     def _set_options(self, args: dict):
         """Stores the constructor arguments both classes take (OPTIONS, out of the constructor's locals()) as
@@ -266,6 +327,10 @@ class _SequenceBase:
         for k in self.OPTIONS:
             setattr(self, k, args[k])
         _check_policy(self.keyframe_policy, self.window)
+        if self.num_frames is not None and not 1 <= len(self.frames) <= int(self.num_frames):
+            raise ValueError(f"num_frames {self.num_frames}: between 1 and num_frames frames to start with")
+        if int(self.map_every) < 1:
+            raise ValueError("map_every >= 1")
         check_densify_args(self.densify_mode, self.densify_frames, self.densify_cam, self.densify_intrinsics,
                            self.frames)
         self.overlap_pixels = int(self.overlap_pixels)
@@ -278,6 +343,27 @@ class _SequenceBase:
         """GraphTracker.track_frame's depth_loss_thres: the configured threshold, or None (option off)."""
         cfg = self.track_cfg
         return float(cfg.depth_loss_thres) if cfg.use_depth_loss_thres else None
+
+    def _n_frames(self) -> int:
+        """The capture's length: num_frames when given (the frame list may still be growing), else the list's."""
+        return len(self.frames) if self.num_frames is None else int(self.num_frames)
+
+    def _maps(self, t: int) -> bool:
+        """Whether frame t densifies and maps (map_every, scripts/splatam_realtime.py:844): frame 0 always."""
+        return t == 0 or (t + 1) % int(self.map_every) == 0
+
+    def _append_frame(self, im: torch.Tensor, depth: torch.Tensor, densify_frame=None) -> int:
+        """A frame that arrived: appended to the frame list (and its densification frame to densify_frames, when
+        the capture has those).  Returns its index; ValueError beyond num_frames (the pose columns)."""
+        t = len(self.frames)
+        if self.num_frames is None or t >= int(self.num_frames):
+            raise ValueError(f"frame {t}: the sequence holds num_frames = {self.num_frames} frames")
+        if (densify_frame is None) != (self.densify_frames is None):
+            raise ValueError("densify_frame: one per frame when the capture has densify_frames, else none")
+        self.frames.append({"im": im, "depth": depth})
+        if densify_frame is not None:
+            self.densify_frames.append(densify_frame)
+        return t
 
     def _kf(self, t: int) -> dict:
         return {"cam": self.cam, "w2c": self.w2c, "im": self.frames[t]["im"], "depth": self.frames[t]["depth"], "id": t}
@@ -298,7 +384,7 @@ class _SequenceBase:
         (scripts/splatam.py:907-913; frame 0 is one from the start) and, "overlap" (:932), frames 0 and num_frames - 2."""
         every = (t + 1) % self.keyframe_every == 0
         if self.keyframe_policy == "overlap":
-            return every or t in (0, len(self.frames) - 2)
+            return every or t in (0, self._n_frames() - 2)
         return every and t > 0
 
     def _word_counts(self, n_kf: int) -> tuple[int, int, int]:
@@ -313,23 +399,25 @@ class SlamSequence(_SequenceBase):
 
     params: the initial map (SplaTAM's init from frame 0; isotropic, rgb colours) with one pose column per frame;
     frames: per frame {"im", "depth"} targets (all sharing `cam` / `w2c`, the first frame's, like the reference);
-    intrinsics (fx, fy, cx, cy).  frame(t) runs one frame; run(frames) a range of them."""
+    intrinsics (fx, fy, cx, cy).  frame(t) runs one frame; run(frames) a range of them; push(im, depth) one that
+    arrives (num_frames given).  params None: the map is init_map_device's, from frames[0]."""
 
     def __init__(self, params: dict, frames: list, cam, w2c, intrinsics, capacity: int, bin_capacity: int,
                  tracking_iters: int = 40, mapping_iters: int = 60, track_replay: int = 20, window: int = 8,
                  keyframe_every: int = 5, sil_thres: float = 0.5, track_cfg: TrackingConfig = TrackingConfig(),
                  map_cfg: MappingConfig = MappingConfig(), prune: bool | None = None, seed: int = 0,
                  scene_radius=None, keyframe_policy: str = "window", overlap_pixels: int = 1600,
-                 densify_mode: str = "torch", densify_frames=None, densify_cam=None, densify_intrinsics=None):
-        if color_key(params) != "rgb_colors" or params["log_scales"].shape[1] != 1:
+                 densify_mode: str = "torch", densify_frames=None, densify_cam=None, densify_intrinsics=None,
+                 median_thr=None, median_scale: float = 50.0, num_frames: int | None = None, map_every: int = 1):
+        if params is not None and (color_key(params) != "rgb_colors" or params["log_scales"].shape[1] != 1):
             raise ValueError("SlamSequence: SplaTAM's isotropic rgb map (the tracking fast path's form)")
         if tracking_iters % track_replay:
             raise ValueError("tracking_iters must be a multiple of track_replay")
         self._set_options(locals())
         self.bin_capacity, self.seed = int(bin_capacity), seed
         self.rng = np.random.RandomState(seed)
-        self.draws = []  # per frame: the mapper's keyframe draws (window indices); "overlap": the random words
-        dev = params["means3D"].device
+        self.draws = []  # per frame: the mapper's keyframe draws (window indices; None: the frame did not map); "overlap": the random words
+        dev = frames[0]["depth"].device if params is None else params["means3D"].device
         if keyframe_policy == "overlap":
             f0 = frames[0]
             self.bank = KeyframeBank(f0["im"].shape, f0["depth"].shape, dev)
@@ -341,12 +429,19 @@ class SlamSequence(_SequenceBase):
         if densify_mode == "device":
             d0 = (densify_frames if densify_frames is not None else frames)[0]["depth"]
             self.densify_workspace = make_densify_workspace(d0.shape[-2], d0.shape[-1], dev)
-        self._build(params, int(capacity))
+        padded = None
+        if params is None:  # the map is born from frame 0 (initialize_first_timestep), on the device
+            kf, intr = self._densify_kf(0)
+            padded = init_map_device(kf, w2c, intr, self._n_frames(), int(capacity), overflow=self.overflow,
+                                     workspace=getattr(self, "densify_workspace", None))
+            params = padded[0]
+        self._build(params, int(capacity), padded)
 
-    def _build(self, params: dict, capacity: int):
-        """The padded map of `params` (its per-Gaussian rows live) and the tracker / mapper graphs over it."""
+    def _build(self, params: dict, capacity: int, padded=None):
+        """The padded map of `params` (its per-Gaussian rows live; `padded`: pad_map's triple, when the caller
+        built it) and the tracker / mapper graphs over it."""
         self.capacity = capacity
-        self.params, self.alive, self.n_live = pad_map(params, self.capacity)
+        self.params, self.alive, self.n_live = pad_map(params, self.capacity) if padded is None else padded
         for k in GAUSS_KEYS + ("rgb_colors",):
             self.params[k].requires_grad_(True)
         q, tr = params["cam_unnorm_rots"], params["cam_trans"]
@@ -403,11 +498,13 @@ class SlamSequence(_SequenceBase):
         kf, intr = self._densify_kf(t)
         if self.densify_mode == "torch":
             densify_static(self.params, self.alive, self.n_live, self.overflow, kf, t, intr,
-                           self.sil_thres, self.capacity, self.bin_capacity, self.dstatus)
+                           self.sil_thres, self.capacity, self.bin_capacity, self.dstatus, self.median_thr,
+                           self.median_scale)
             return
         ds = render_depth_sil(self.params, kf, t, self.alive, self.bin_capacity, self.dstatus)
         densify_device(self.params, self.alive, self.n_live, self.overflow, kf, pose_w2c(self.params, t), intr,
-                       self.sil_thres, self.capacity, ds, self.densify_workspace)
+                       self.sil_thres, self.capacity, ds, self.densify_workspace, median_thr=self.median_thr,
+                       median_scale=self.median_scale)
 
     def map(self, t: int, sequence=None):
         """The mapping frame over the window (the last window - 1 keyframes + frame t), keyframe draws from the
@@ -421,7 +518,17 @@ class SlamSequence(_SequenceBase):
         self.draws.append(seq)
         self.mapper.run(check=False, sequence=seq)
         self._compact_pruned()
-        if self._is_keyframe(t):
+        self._add_keyframe(t)
+
+    def _add_keyframe(self, t: int):
+        """The keyframe bookkeeping after a frame (scripts/splatam.py:907-913, 932-945), mapped or not."""
+        if not self._is_keyframe(t):
+            return
+        if self.keyframe_policy == "overlap":
+            f = self.frames[t]
+            if self.bank.append(f["im"], f["depth"], self.params, t):  # (the bank doubled: new tensors)
+                self.mapper.set_keyframe_bank(self.bank.im, self.bank.depth)
+        else:
             self.keyframes.append(self._kf(t))
 
     def _compact_pruned(self):
@@ -448,18 +555,42 @@ class SlamSequence(_SequenceBase):
         self.selections.append(sel)
         self.mapper.run(check=False, device_sequence=(sel["draw_rows"], sel["draw_times"]))
         self._compact_pruned()
-        if self._is_keyframe(t):
-            if bank.append(f["im"], f["depth"], self.params, t):  # (the bank doubled: new tensors)
-                self.mapper.set_keyframe_bank(bank.im, bank.depth)
+        self._add_keyframe(t)
 
-    def frame(self, t: int, sequence=None):
-        """One frame of scripts/splatam.py:697-929: tracking (t > 0), densification (t > 0), mapping."""
+    def frame(self, t: int, sequence=None, w2c=None):
+        """One frame of scripts/splatam.py:697-929: tracking (t > 0), densification (t > 0), mapping.
+        w2c (device [4,4], the frame's pose relative to frame 0; tracking.use_gt_poses): the frame is not tracked,
+        write_given_pose fills column t (ignored for frame 0, whose column is the identity).  A frame that does
+        not map (map_every) does not densify either; its keyframe bookkeeping still runs."""
         ran = 0
         if t > 0:
-            ran = self.track(t)
-            self.densify(t)
+            if w2c is None:
+                ran = self.track(t)
+            else:
+                write_given_pose(self.params, t, w2c)
+            if self._maps(t):
+                self.densify(t)
         self.tracking_iters_run.append(ran)
-        self.map(t, sequence)
+        if self._maps(t):
+            self.map(t, sequence)
+        else:
+            self.draws.append(None)
+            self._add_keyframe(t)
+
+    def run(self, frames=None):
+        """frame(t) for every t of `frames` (an iterable; default: the frames in the list that have not run)."""
+        for t in (range(len(self.tracking_iters_run), len(self.frames)) if frames is None else frames):
+            self.frame(t)
+
+    def push(self, im: torch.Tensor, depth: torch.Tensor, w2c=None, densify_frame=None) -> int:
+        """A frame that arrives (the realtime loop, scripts/splatam_realtime.py): appended to the frame list and
+        run as frame t = len(frames) - 1, with its pose when `w2c` is given (frame()).  Needs num_frames: the
+        pose tensors have that many columns, and a frame beyond them raises ValueError.  densify_frame
+        {"im", "depth"}: the frame at the densification resolution, for a capture with densify_frames.
+        Returns t.  Nothing is read back (but see track_cfg.use_depth_loss_thres)."""
+        t = self._append_frame(im, depth, densify_frame)
+        self.frame(t, w2c=w2c)
+        return t
 
     def check(self):
         """One host synchronisation: raises if a binning capacity or the map capacity overflowed."""
@@ -510,16 +641,19 @@ class PerFrameSlam(_SequenceBase):
                  sil_thres: float = 0.5, track_cfg: TrackingConfig = TrackingConfig(),
                  map_cfg: MappingConfig = MappingConfig(), prune: bool | None = None, scene_radius=None,
                  bin_capacity: int | None = None, keyframe_policy: str = "window", overlap_pixels: int = 1600,
-                 densify_mode: str = "torch", densify_frames=None, densify_cam=None, densify_intrinsics=None):
+                 densify_mode: str = "torch", densify_frames=None, densify_cam=None, densify_intrinsics=None,
+                 median_thr=None, median_scale: float = 50.0, num_frames: int | None = None, map_every: int = 1):
         self._set_options(locals())
         self.kf_list = []  # "overlap": the keyframes in the order appended, each with its est_w2c snapshot
         self.windows = []  # "overlap": per frame, the selected window's time indices
         self.p = {k: v.detach().clone() for k, v in params.items()}
 
-    def frame(self, t: int, sequence):
+    def frame(self, t: int, sequence, w2c=None):
         p = self.p
         ran = 0
-        if t > 0:
+        if t > 0 and w2c is not None:
+            write_given_pose(p, t, w2c)
+        elif t > 0:
             initialize_camera_pose(p, t)
             tp = dict(p)
             tp["cam_unnorm_rots"] = p["cam_unnorm_rots"][..., t:t + 1].clone().requires_grad_(True)
@@ -532,10 +666,14 @@ class PerFrameSlam(_SequenceBase):
             with torch.no_grad():
                 p["cam_unnorm_rots"][..., t] = tp["cam_unnorm_rots"][..., 0]
                 p["cam_trans"][..., t] = tp["cam_trans"][..., 0]
+        if t > 0 and self._maps(t):
             kf, intr = self._densify_kf(t)
             add = add_new_gaussians_device if self.densify_mode == "device" else add_new_gaussians_literal
-            p = add(p, kf, t, intr, self.sil_thres)
+            p = add(p, kf, t, intr, self.sil_thres, self.median_thr, self.median_scale)
         self.tracking_iters_run.append(ran)
+        if not self._maps(t):
+            self._add_keyframe(t)
+            return
         mp = {k: (v.detach().requires_grad_(True) if k in GAUSS_KEYS + ("rgb_colors",) else v) for k, v in p.items()}
         if self.keyframe_policy == "overlap":
             win, sequence = self._select_overlap(p, t, sequence)
@@ -547,11 +685,15 @@ class PerFrameSlam(_SequenceBase):
         if m.prune_at:
             mp, _, _ = m.compact()
         self.p = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in mp.items()}
-        if self._is_keyframe(t):
-            if self.keyframe_policy == "overlap":
-                self.kf_list.append(dict(self._kf(t), est_w2c=pose_w2c(self.p, t)))
-            else:
-                self.keyframes.append(self._kf(t))
+        self._add_keyframe(t)
+
+    def _add_keyframe(self, t: int):
+        if not self._is_keyframe(t):
+            return
+        if self.keyframe_policy == "overlap":
+            self.kf_list.append(dict(self._kf(t), est_w2c=pose_w2c(self.p, t)))
+        else:
+            self.keyframes.append(self._kf(t))
 
     def _select_overlap(self, p: dict, t: int, words):
         """keyframes.select_literal on the frame's random words (SlamSequence.draws[t]): the window's keyframe

@@ -32,6 +32,29 @@ def build_rotation(q):
     return R.reshape(-1, 3, 3)
 
 
+def matrix_to_quaternion(matrix: torch.Tensor) -> torch.Tensor:
+    """slam_helpers.py:43-103 (pytorch3d's): rotation matrices [..., 3, 3] to quaternions [..., 4], real part
+    first, from the best-conditioned of the four candidates (the largest of |r|, |i|, |j|, |k|; the first on
+    a tie, as argmax).  Elementwise ops, where and gather: no host read, no boolean indexing."""
+    if matrix.size(-1) != 3 or matrix.size(-2) != 3:
+        raise ValueError(f"Invalid rotation matrix shape {matrix.shape}.")
+    batch = matrix.shape[:-2]
+    m00, m01, m02, m10, m11, m12, m20, m21, m22 = torch.unbind(matrix.reshape(batch + (9,)), dim=-1)
+    sq = torch.stack([1.0 + m00 + m11 + m22, 1.0 + m00 - m11 - m22, 1.0 - m00 + m11 - m22,
+                      1.0 - m00 - m11 + m22], dim=-1)
+    q_abs = torch.where(sq > 0, torch.sqrt(sq.clamp_min(0)), torch.zeros_like(sq))  # _sqrt_positive_part
+    q2 = q_abs ** 2
+    quat_by_rijk = torch.stack([
+        torch.stack([q2[..., 0], m21 - m12, m02 - m20, m10 - m01], dim=-1),
+        torch.stack([m21 - m12, q2[..., 1], m10 + m01, m02 + m20], dim=-1),
+        torch.stack([m02 - m20, m10 + m01, q2[..., 2], m12 + m21], dim=-1),
+        torch.stack([m10 - m01, m20 + m02, m21 + m12, q2[..., 3]], dim=-1)], dim=-2)
+    flr = torch.tensor(0.1, dtype=q_abs.dtype, device=q_abs.device)
+    cand = quat_by_rijk / (2.0 * q_abs[..., None].max(flr))
+    best = q_abs.argmax(dim=-1)
+    return torch.gather(cand, -2, best[..., None, None].expand(batch + (1, 4))).reshape(batch + (4,))
+
+
 def quat_mult(q1, q2):
     """slam_helpers.py quat_mult (Hamilton product, w first)."""
     w1, x1, y1, z1 = q1.T
