@@ -16,6 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 OBJDIR = os.path.join(HERE, "_build")
+INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(HERE, "libgsr.so")
 DIAG = os.path.join(HERE, "_diag")  # experiment / diagnostics libraries that travel to the GPU box
 SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_backward_power.hip", "gsr_capi.hip", "gsr_timing.hip",
@@ -31,39 +32,48 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found: the MI355X build needs ROCm's hipcc")
 
 
-def flags():
+def flags(csrc: str = CSRC, include: str = INCLUDE):
     # -fno-slp-vectorize: keep f32 adds/muls single-issue; SLP packing into v_pk_*_f32
     # splits every DPP-fused add into v_mov_b32_dpp + v_pk_add (cdna_hip_programming.md App. B).
     return ["-std=c++17", "-O3", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function",
             "-fno-slp-vectorize",
-            "-I", os.path.join(ROOT, "include"), "-I", CSRC]
+            "-I", include, "-I", csrc]
 
 
-def _compile(src: str, objdir: str = OBJDIR, extra=()) -> str:
+def _compile(src: str, objdir: str = OBJDIR, extra=(), csrc: str = CSRC, include: str = INCLUDE) -> str:
     obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
-    srcp = os.path.join(CSRC, src)
-    deps = [srcp, os.path.join(ROOT, "include", "gsr.h"), os.path.join(ROOT, "include", "gsr_glue.h")] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
+    srcp = os.path.join(csrc, src)
+    deps = [srcp, os.path.join(include, "gsr.h"), os.path.join(include, "gsr_glue.h")] + [os.path.join(csrc, h) for h in os.listdir(csrc) if h.endswith(".h")]
     if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(d) for d in deps):
         return obj
-    cmd = [hipcc(), *flags(), *extra, "-c", srcp, "-o", obj]
+    cmd = [hipcc(), *flags(csrc, include), *extra, "-c", srcp, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
-        raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
+        raise RuntimeError(f"hipcc failed for {srcp}:\n{r.stdout}\n{r.stderr}")
     return obj
 
 
-def build(force: bool = False) -> str:
-    os.makedirs(OBJDIR, exist_ok=True)
-    if force:
-        for f in os.listdir(OBJDIR):
-            os.remove(os.path.join(OBJDIR, f))
-    with ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
-        objs = list(ex.map(_compile, SOURCES))
-    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(o) for o in objs):
-        cmd = [hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB, *objs]
+def _compile_all(objdir: str, extra=(), csrc: str = CSRC, include: str = INCLUDE):
+    """Every translation unit of SOURCES compiled into `objdir` (stale objects only); the object paths."""
+    os.makedirs(objdir, exist_ok=True)
+    with ThreadPoolExecutor(max_workers=min(16, len(SOURCES))) as ex:
+        return list(ex.map(lambda s: _compile(s, objdir, extra, csrc, include), SOURCES))
+
+
+def _link(objs, lib: str) -> str:
+    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(o) for o in objs):
+        cmd = [hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib, *objs]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    return lib
+
+
+def build(force: bool = False) -> str:
+    if force and os.path.isdir(OBJDIR):
+        for f in os.listdir(OBJDIR):
+            os.remove(os.path.join(OBJDIR, f))
+    _link(_compile_all(OBJDIR), LIB)
     build_torch_binding(force=force)
     return LIB
 
@@ -112,34 +122,17 @@ def build_diag() -> str:
     """Diagnostics library (tools/wgtime.py): libgsr with -DGSR_WGTIME=1 (per-workgroup render timelines),
     built to splatam_amd/_build_diag/libgsr_diag.so; loaded only through GSR_LIB by the diagnostics tool."""
     objdir = os.path.join(HERE, "_build_diag")
-    os.makedirs(objdir, exist_ok=True)
-    with ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
-        objs = list(ex.map(lambda s: _compile(s, objdir, ("-DGSR_WGTIME=1",)), SOURCES))
-    lib = os.path.join(objdir, "libgsr_diag.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(o) for o in objs):
-        r = subprocess.run([hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib, *objs],
-                           capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
-    return lib
+    return _link(_compile_all(objdir, ("-DGSR_WGTIME=1",)), os.path.join(objdir, "libgsr_diag.so"))
 
 
 def build_variant(tag: str, defines=()) -> str:
-    """Timing-experiment library (tools/gpu_round.sh ab= / abbench= steps): libgsr built with extra -D flags into
-    splatam_amd/_build_<tag>/libgsr_<tag>.so; loaded only through GSR_LIB."""
+    """Instrument library (the measuring macros of csrc/gsr_diag.h, e.g. tools/gpu_round.sh's sqab= step): libgsr
+    built with extra -D flags into splatam_amd/_build_<tag>/libgsr_<tag>.so; loaded only through GSR_LIB.
+    An A/B of two implementations goes through build_from_rev, not through a macro in the sources."""
     objdir = os.path.join(HERE, f"_build_{tag}")
-    os.makedirs(objdir, exist_ok=True)
     if isinstance(defines, dict):  # {"NAME": "value"} -> NAME=value (iterating a dict would drop the values)
         defines = [f"{k}={v}" for k, v in defines.items()]
-    extra = tuple(f"-D{d}" for d in defines)
-    with ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
-        objs = list(ex.map(lambda s: _compile(s, objdir, extra), SOURCES))
-    lib = os.path.join(objdir, f"libgsr_{tag}.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(o) for o in objs):
-        r = subprocess.run([hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib, *objs],
-                           capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    lib = _link(_compile_all(objdir, tuple(f"-D{d}" for d in defines)), os.path.join(objdir, f"libgsr_{tag}.so"))
     # the _build_<tag> trees stay on this machine (.gpurunignore); the experiment's library travels to the
     # GPU box from splatam_amd/_diag/ (delete that directory when the experiment is done)
     os.makedirs(DIAG, exist_ok=True)
@@ -147,39 +140,29 @@ def build_variant(tag: str, defines=()) -> str:
     return os.path.join(DIAG, f"libgsr_{tag}.so")
 
 
+def export_rev(rev: str, work: str):
+    """The csrc/ and include/ trees of git revision `rev` exported under `work`; their two paths."""
+    import io
+    import tarfile
+    for sub in ("splatam_amd/csrc", "include"):
+        r = subprocess.run(["git", "-C", ROOT, "archive", rev, sub], capture_output=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"git archive {rev} {sub} failed: {r.stderr.decode(errors='replace')}")
+        with tarfile.open(fileobj=io.BytesIO(r.stdout)) as tf:
+            tf.extractall(work)
+    return os.path.join(work, "splatam_amd", "csrc"), os.path.join(work, "include")
+
+
 def build_from_rev(rev: str, tag: str) -> str:
     """A/B baseline without macros in the sources: libgsr built from the csrc/ and include/ trees of git
     revision `rev` (exported to a scratch directory) into splatam_amd/_diag/libgsr_<tag>.so, which
     tools/gpu_round.sh's ab= / abbench= steps load through GSR_LIB."""
-    import io
-    import tarfile
     import tempfile
     work = tempfile.mkdtemp(prefix=f"gsr_{tag}_")
     try:
-        for sub in ("splatam_amd/csrc", "include"):
-            r = subprocess.run(["git", "-C", ROOT, "archive", rev, sub], capture_output=True)
-            if r.returncode != 0:
-                raise RuntimeError(f"git archive {rev} {sub} failed: {r.stderr.decode(errors='replace')}")
-            with tarfile.open(fileobj=io.BytesIO(r.stdout)) as tf:
-                tf.extractall(work)
-        csrc, inc = os.path.join(work, "splatam_amd", "csrc"), os.path.join(work, "include")
-        objs = []
-        for src in SOURCES:
-            obj = os.path.join(work, os.path.splitext(src)[0] + ".o")
-            base = flags()
-            base = [f for i, f in enumerate(base) if f != "-I" and (i == 0 or base[i - 1] != "-I")]  # (drop -I pairs)
-            cmd = [hipcc(), *base, "-I", inc, "-I", csrc, "-c", os.path.join(csrc, src), "-o", obj]
-            r = subprocess.run(cmd, capture_output=True, text=True)
-            if r.returncode != 0:
-                raise RuntimeError(f"hipcc failed for {src} at {rev}:\n{r.stderr}")
-            objs.append(obj)
+        csrc, inc = export_rev(rev, work)
         os.makedirs(DIAG, exist_ok=True)
-        lib = os.path.join(DIAG, f"libgsr_{tag}.so")
-        r = subprocess.run([hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib, *objs],
-                           capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"link failed:\n{r.stderr}")
-        return lib
+        return _link(_compile_all(work, (), csrc, inc), os.path.join(DIAG, f"libgsr_{tag}.so"))
     finally:
         shutil.rmtree(work, ignore_errors=True)
 

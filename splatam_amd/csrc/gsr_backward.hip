@@ -22,21 +22,15 @@
 #include "gsr_glue_common.h"
 #include "gsr_render_fwd.h"
 
-#ifndef GSR_PK_XD
-#define GSR_PK_XD 1  // the tile walk's e Tn and alpha Tn as one packed multiply
-#endif
-#ifndef GSR_POSE_TAIL
-#define GSR_POSE_TAIL 2  // levels of the fused pose reduction's last-workgroup sum (1 or 2)
-#endif
-
 namespace gsr {
 
 // Per-pair geometric terms (hx, hy, hx dx, hx dy, hy dy[, G dL/dalpha]) with
 // h = G * dL/dG = (o * G) * dL/dalpha.
 template <bool OPAC>
 __device__ __forceinline__ void pair_geom(float* vk, float araw, float dLa, float G, v2f d) {
-#if GSR_PK_XD
-    if constexpr (OPAC) {  // (araw dLa, G dLa): one v_pk_mul_f32, the same two products
+    // (araw dLa, G dLa), like the walk's (e Tn, alpha Tn), as one v_pk_mul_f32: the same two products, bitwise
+    // the same sums as two v_mul_f32, 2 VALU per pair less (profiles/r8h_ab_pk_reduce.txt)
+    if constexpr (OPAC) {
         const v2f ho = v2f{araw, G} * dLa;
         const v2f hv = ho.x * d;
         const v2f hh = hv.x * d;
@@ -48,7 +42,6 @@ __device__ __forceinline__ void pair_geom(float* vk, float araw, float dLa, floa
         vk[5] = ho.y;
         return;
     }
-#endif
     const v2f hv = (araw * dLa) * d;  // (hx, hy)
     const v2f hh = hv.x * d;          // (hx dx, hx dy)
     vk[0] = hv.x;
@@ -231,16 +224,6 @@ __device__ __forceinline__ void mom_matrix(const float* S, float (&Sm)[9][9], st
 #ifndef GSR_BWD_MAP_WAVES
 #define GSR_BWD_MAP_WAVES 4
 #endif
-#ifndef GSR_BWD_SPLIT6
-#define GSR_BWD_SPLIT6 1  // wide variants: the first reduction pass carries G dL/dalpha with the 5 geometric sums
-// (6 + 6 instead of 5 + 7 sums for mapping: 84 instead of 96 DPP adds per step, render_bwd 312 -> 303 us at config 4)
-#endif
-#ifndef GSR_NT_STORES
-#define GSR_NT_STORES 0  // render kernels' record / image stores as non-temporal (streaming) stores
-#endif
-#ifndef GSR_PACK_C
-#define GSR_PACK_C 1  // DUAL, Q2 = 1: the second colour set's one channel staged in s_c.w (no s_d array)
-#endif
 template <bool DUAL, bool OPAC, bool COL1, bool COL2, int Q2, int MOM = 0>
 constexpr int bwd_waves() {
     return MOM ? 4 : ((DUAL && Q2 == 3) ? GSR_BWD_MAP_WAVES : ((OPAC && COL1) ? GSR_BWD_WIDE_WAVES : 5));
@@ -264,7 +247,9 @@ struct BwdShape {
     static constexpr int SL = BB + 1;
     // PACKC: the dual render's second colour set needs only channel 0 (Q2 = 1): staged as s_c.w (the
     // tile-rect half s_c.w carried is consumed at staging), so a pair reads one colour float4, not two
-    static constexpr bool PACKC = GSR_PACK_C && DUAL && Q2 == 1;
+    // (no s_d array; the two-float4 staging measured 74 against 72.5 us on the config-3 dual lean launch,
+    // profiles/r3_ab_render_bwd.txt)
+    static constexpr bool PACKC = DUAL && Q2 == 1;
     static constexpr size_t o_a = 0, o_b = o_a + 16 * SL, o_c = o_b + 16 * SL, o_d = o_c + 16 * SL;
     static constexpr size_t o_acc = o_d + 16 * ((DUAL && !PACKC) ? SL : 1);
     static constexpr size_t o_list = o_acc + (4 * (BS + 1) * NV + 15) / 16 * 16;
@@ -493,13 +478,9 @@ __device__ __forceinline__ void bwd_tile(const Camera& cam, int tile, const BwdP
             for (int k = 0; k < 4; k++) {
                 const float4 c = rec(s_c, k);
                 float cd;
-                if (DUAL && Q2 == 1 && PACKC) {  // (c.x, c.y) . dp01 + (c.z, c.w) . (dp2, dq0): pk_mul + pk_fma + add
+                if (PACKC) {  // (c.x, c.y) . dp01 + (c.z, c.w) . (dp2, dq0): pk_mul + pk_fma + add
                     const v2f t = __builtin_elementwise_fma(v2f{c.z, c.w}, dp2q0, v2f{c.x, c.y} * dp01);
                     cd = t.x + t.y;
-                } else if (DUAL && Q2 == 1) {
-                    const float c2x = rec(s_d, k).x;
-                    const v2f t = v2f{c.x, c.y} * dp01;
-                    cd = __builtin_fmaf(c.z, dp2, __builtin_fmaf(c2x, dq0, t.x + t.y));
                 } else if (DUAL) {
                     const float4 c2 = rec(s_d, k);
                     const v2f t = v2f{c.x, c.y} * dp01 + v2f{c2.x, c2.y} * dq01;
@@ -513,14 +494,9 @@ __device__ __forceinline__ void bwd_tile(const Camera& cam, int tile, const BwdP
                 const float inv = __builtin_amdgcn_rcpf(1.f - alpha[k]);   // v_rcp_f32 (~1 ulp)
                 const float Tn = T * inv;                                   // T / (1 - alpha), backward.cu:978
                 const float e = cd - A;
-#if GSR_PK_XD
                 const v2f xd = v2f{e, alpha[k]} * Tn;  // (e Tn, alpha Tn): one v_pk_mul_f32, the same two products
                 const float x = xd.x;
                 dch[k] = xd.y;                          // 0 when masked
-#else
-                const float x = e * Tn;
-                dch[k] = alpha[k] * Tn;                 // 0 when masked
-#endif
                 dLa[k] = (OPAC && !ok[k]) ? 0.f : x;    // (without OPAC: h = araw dLa is 0 when masked)
                 T = Tn;  // masked pairs: alpha = 0 and v_rcp_f32(1) == 1 exactly (tools/micro/rcp_one.hip)
                 A = __builtin_fmaf(alpha[k], e, A);     // unchanged when masked
@@ -534,12 +510,8 @@ __device__ __forceinline__ void bwd_tile(const Camera& cam, int tile, const BwdP
                 MomIn e[4];
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
-#if GSR_PK_XD
                     const v2f ho = v2f{araw[k], G[k]} * dLa[k];
                     const float h = ho.x, o = ho.y;
-#else
-                    const float h = araw[k] * dLa[k], o = G[k] * dLa[k];
-#endif
                     const float hx = h * d[k].x, hy = h * d[k].y;
                     e[k].m20 = hx * hx;
                     e[k].m11 = hx * hy;
@@ -583,22 +555,21 @@ __device__ __forceinline__ void bwd_tile(const Camera& cam, int tile, const BwdP
                 } else {
                     reduce_store<NV>(v, lane, dst, true);
                 }
-            } else {  // wide variants: geometric (+ opacity), then colour sums (register pressure)
-                constexpr bool OP_A = OPAC && GSR_BWD_SPLIT6;
-                constexpr int NA = 5 + (OP_A ? 1 : 0), NB = NV - NA;
+            } else {  // wide variants: geometric (+ opacity), then colour sums (register pressure).  G dL/dalpha
+                // rides with the 5 geometric sums: 6 + 6 instead of 5 + 7 sums for mapping is 84 instead of 96 DPP
+                // adds per step (render_bwd 312 -> 303 us at config 4, profiles/r3_split_ab.txt)
+                constexpr int NA = 5 + (OPAC ? 1 : 0), NB = NV - NA;
                 {
                     float v[4 * NA];
 #pragma unroll
-                    for (int k = 0; k < 4; k++) pair_geom<OP_A>(v + NA * k, araw[k], dLa[k], G[k], d[k]);
+                    for (int k = 0; k < 4; k++) pair_geom<OPAC>(v + NA * k, araw[k], dLa[k], G[k], d[k]);
                     reduce_store<NA>(v, lane, dst, true);
                 }
                 {
                     float v[4 * NB];
-                    constexpr int OB = (OPAC && !OP_A) ? 1 : 0;
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
-                        if (OB) v[NB * k] = G[k] * dLa[k];
-                        pair_colours<COL1, COL2, Q2, C1>(v + NB * k + OB, dch[k], dp01, dp2, dq0, dq01, dq2);
+                        pair_colours<COL1, COL2, Q2, C1>(v + NB * k, dch[k], dp01, dp2, dq0, dq01, dq2);
                     }
                     reduce_store<NB>(v, lane, dst + NA, true);
                 }
@@ -632,11 +603,10 @@ __device__ __forceinline__ void bwd_tile(const Camera& cam, int tile, const BwdP
 #pragma unroll
             for (int i = 0; i < NQR; i++)
                 if (q + TPE * i < RS) {
-                    // (streaming stores measured neutral for render_bwd and 3-9 us slower for the gauss_bwd that
-                    // reads the records next: profiles/r4l_ab_nt.txt, r4m_ab_nt.txt)
+                    // (plain stores: streaming stores measured neutral for render_bwd and 3-9 us slower for the
+                    // gauss_bwd that reads the records next: profiles/r4l_ab_nt.txt, r4m_ab_nt_tail.txt)
                     const float val = i < NQ ? c[i] : 0.f;  // (C1 = 1: the two absent colour sums are zero)
-                    if (GSR_NT_STORES) __builtin_nontemporal_store(val, &dst[q + TPE * i]);
-                    else dst[q + TPE * i] = val;
+                    dst[q + TPE * i] = val;
                 }
         }
         dg.phase(5);
@@ -982,53 +952,14 @@ __device__ __forceinline__ void gauss_bwd_body(Camera cam, GaussIn g, GeomPtrs g
         float* const part = scratch_partials(pf.scratch);
         if (threadIdx.x < POSE_PARTS) st_agent(part + POSE_PARTS * blockIdx.x + threadIdx.x, s_tot[threadIdx.x]);
         if constexpr (kAblate == 3) return;  // timing ablation: no pose tail (invalid pose update)
-#if GSR_POSE_TAIL == 1
-        // One-level fixed-order sum: the last workgroup to arrive (grouped arrival counters) reads
-        // all partials as one coalesced float stream (thread t: floats t, t + 256, ... = value
-        // k = t % 16 of the partials t / 16, t / 16 + 16, ... in order, 40 loads in flight per round
-        // trip), then adds the 16 classes of each value in order through LDS.  Three serial memory
-        // round trips (publish, arrive, gather) instead of the two-level tail's six.
-        {
-            const int nb = gridDim.x;
-            if (!last_block_arrive_grouped(scratch_counters(pf.scratch))) return;
-            if constexpr (kAblate == 4) return;  // timing ablation: arrival only
-            static_assert(256 % POSE_PARTS == 0, "a thread keeps one value index");
-            constexpr int CH = 40;
-            const int total = POSE_PARTS * nb;
-            float acc = 0.f;
-            for (int f0 = threadIdx.x; f0 < total; f0 += CH * 256) {
-                float buf[CH];
-#pragma unroll
-                for (int u = 0; u < CH; u++) {
-                    const int f = f0 + 256 * u;
-                    buf[u] = f < total ? ld_agent(part + f) : 0.f;
-                }
-#pragma unroll
-                for (int u = 0; u < CH; u++) acc += buf[u];
-            }
-            __shared__ float s_cls[256];
-            s_cls[threadIdx.x] = acc;
-            __syncthreads();
-            if (threadIdx.x < POSE_PARTS) {
-                float t = 0.f;
-#pragma unroll
-                for (int c = 0; c < 256 / POSE_PARTS; c++) t += s_cls[threadIdx.x + POSE_PARTS * c];
-                s_tot[threadIdx.x] = t;
-            }
-            __syncthreads();
-            if (kAblate != 5 && threadIdx.x == 0) {  // (5: timing ablation, no pose_fin)
-                const PoseAdam adam{pf.lr_q, pf.lr_t, pf.beta1, pf.beta2, (float)(1.0 - pf.beta1),
-                                    (float)(1.0 - pf.beta2), (float)pf.eps, pf.adam_state, pf.cam_q, pf.cam_t,
-                                    pf.guard, pf.cap, pf.loss, pf.best};
-                pose_fin(s_tot, pf.cam_q, pf.qs, pf.dq, pf.dt, adam);
-            }
-            return;
-        }
-#endif
         // Two-level fixed-order sum of the ~1200 workgroup partials: the last workgroup of each
         // of the 16 arrival groups (b = g mod 16) adds its group's partials (one per thread)
         // and publishes the group sum; the last group then adds the 16 group sums.  (One
-        // workgroup reading all partials serially cost ~18 us more than the separate pose kernel.)
+        // workgroup reading all partials serially cost ~18 us more than the separate pose kernel.  A one-level
+        // tail -- the last workgroup gathers all partials as one coalesced stream, 40 agent loads in flight per
+        // thread: three serial memory round trips instead of six -- measured no faster, 6350-6367 against
+        // 6379-6397 frames/s, and its other sum order put the config-5 trajectory at 5.3e-4 against the 5e-4
+        // bound: profiles/r7k_ab_pose_finish_kernel.txt.)
         const int nb = gridDim.x;
         uint32_t* ctr = scratch_counters(pf.scratch);
         float* gsum = part + POSE_PARTS * nb;

@@ -20,9 +20,6 @@
 #include "../../include/gsr_glue.h"
 #include "gsr_host.h"
 
-#ifndef GSR_TILE_CULL
-#define GSR_TILE_CULL 1  // Camera::cull for gsr_settings.binning == GSR_BINNING_CULLED (0: A/B builds without culling)
-#endif
 using namespace gsr;
 
 namespace {
@@ -315,7 +312,7 @@ struct Forward {
         if (c.xf) g.xf = *c.xf;  // tracking transform fused into preprocess (g's arrays are then its outputs)
         cam.pre_shift = GL.shift;
         // tile culling: a per-call choice (gsr_settings.binning), no process-wide mode
-        cam.cull = (GSR_TILE_CULL && c.settings->binning != GSR_BINNING_REFERENCE) ? 1 : 0;
+        cam.cull = c.settings->binning != GSR_BINNING_REFERENCE ? 1 : 0;
         cam.tail_exact = eager ? 1 : 0;  // (include/gsr.h: the culled instances, or padding in static mode)
     }
     uint32_t* status() const { return eager ? nullptr : c.status; }

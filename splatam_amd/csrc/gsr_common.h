@@ -201,26 +201,21 @@ __device__ __forceinline__ uint32_t culled_below(uint32_t live, uint32_t k) {
     const uint32_t m = k >= 32u ? 0xFFFFFFFFu : ((1u << k) - 1u);
     return (uint32_t)__popc(~live & m);
 }
-// Wave priority by remaining work (GSR_PRIO_SCHED): the instruction arbiter favours older
+// Wave priority by remaining work: the instruction arbiter favours older
 // waves, so on a CU the last-dispatched tile used to run alone at the end at one wave per
 // SIMD; raising the priority of the waves with the most work left keeps the CU's tiles
 // finishing together (a dynamic longest-remaining-first among co-resident tiles).
-#ifndef GSR_PRIO_SCHED
-#define GSR_PRIO_SCHED 1
-#endif
 // Levels at 70 / 45 / 22 % of the frame's mean tile list (`mean4` = 4 x mean, from num_rendered) when every tile
 // is resident at once (config 3: 1200 tiles, 1280 workgroup slots; 200 / 100 / 50 % measured 3 us slower
 // there), and at 200 / 100 / 50 % when the tiles take several dispatch rounds (config 4: 3225 tiles; the
 // single-round levels measured 392 against 383 us for render_bwd): `multi` = more tiles than 5 per CU.
 __device__ __forceinline__ void prio_by_remaining(int remaining, uint32_t mean4, bool multi) {
-#if GSR_PRIO_SCHED
     const uint32_t r = 4u * (uint32_t)remaining;  // compare r / mean4 against the level thresholds (x 100)
     const uint32_t t3 = multi ? 200u : 70u, t2 = multi ? 100u : 45u, t1 = multi ? 50u : 22u;
     if (100u * r > t3 * mean4) __builtin_amdgcn_s_setprio(3);
     else if (100u * r > t2 * mean4) __builtin_amdgcn_s_setprio(2);
     else if (100u * r > t1 * mean4) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
-#endif
 }
 __device__ __forceinline__ bool sched_multi_round(const Camera& cam) { return cam.gx * cam.gy > 5 * cam.sched_cus; }
 __device__ __forceinline__ uint32_t sched_mean4(const Camera& cam, const uint32_t* counters) {
@@ -633,10 +628,8 @@ __device__ __forceinline__ uint32_t mask_of_geom(const MaskGeom& g, float x0, fl
 }
 // Whether the ellipse can reach the tile at all (Camera::cull): mask_of_geom's test with the tile's whole
 // pixel-centre span [y0, y0 + 15] as one row and [x0, x0 + 15] as one column -- a superset of the union of its
-// sixteen block tests (it also admits the unit gaps between block rows / columns), so conservative like them
-#ifndef GSR_CULL_EXACT
-#define GSR_CULL_EXACT 0  // 1: the sixteen block tests (block_mask_exact != 0) instead
-#endif
+// sixteen block tests (it also admits the unit gaps between block rows / columns), so conservative like them;
+// one test per rect tile instead of the sixteen of mask_of_geom(...) != 0
 __device__ __forceinline__ bool tile_reached(const MaskGeom& g, float x0, float y0) {
     if (g.hx < 0.f) return true;
     if (g.hy < 0.f) return false;
@@ -1075,12 +1068,6 @@ __device__ __forceinline__ void wave_reduce2x9(const float (&v)[18], float (&r)[
 // ends up with NV values of entry e; further transposed steps split m while the
 // count stays even, plain DPP adds finish the rest.  Cost ~2.8 VALU per value
 // against 4 for four plain DPP steps per value.
-#ifndef GSR_DPP_BANKMASK
-#define GSR_DPP_BANKMASK 1
-#endif
-#ifndef GSR_REDUCE_PIN
-#define GSR_REDUCE_PIN 1
-#endif
 template <int NV>
 struct RowReduce {
     static constexpr int V = 4 * NV;
@@ -1136,13 +1123,8 @@ __device__ __forceinline__ void row_reduce(const float (&v)[4 * NV], float (&r)[
     using RR = RowReduce<NV>;
     constexpr int V = RR::V;
     float a[V / 2], b[V / 4];
-#if GSR_DPP_BANKMASK
     row_tstep_ror8<V>(v, a);                    // row_ror:8, bank-masked pair adds
     row_tstep_mirror<V / 2>(a, b);              // row_half_mirror, bank-masked pair adds
-#else
-    row_tstep<V, 0x128>(v, a, lane & 8);        // row_ror:8
-    row_tstep<V / 2, 0x141>(a, b, lane & 4);    // row_half_mirror
-#endif
     if constexpr (RR::S == 2) {
 #pragma unroll
         for (int i = 0; i < RR::R; i++) {
@@ -1159,13 +1141,12 @@ __device__ __forceinline__ void row_reduce(const float (&v)[4 * NV], float (&r)[
         row_tstep<V / 4, 0x4E>(b, c, lane & 2);
         row_tstep<V / 8, 0xB1>(c, r, lane & 1);
     }
-#if GSR_REDUCE_PIN
     // the totals formed here, in every lane: otherwise the compiler sinks the plain steps' adds into the
     // caller's writer-lane branch, where a DPP read of a disabled lane is invalid, so each step becomes
-    // v_mov_b32_dpp (outside) + v_add_f32 (inside) instead of one v_add_f32_dpp (same operands, same sum)
+    // v_mov_b32_dpp (outside) + v_add_f32 (inside) instead of one v_add_f32_dpp (same operands, same sum:
+    // 51 -> 45 reduction VALU per walk step, profiles/r8h_ab_pk_reduce.txt)
 #pragma unroll
     for (int i = 0; i < RR::R; i++) asm volatile("" : "+v"(r[i]));
-#endif
 }
 __device__ __forceinline__ int row_entry(int lane) { return 2 * ((lane >> 3) & 1) + ((lane >> 2) & 1); }
 template <int NV>
@@ -1376,36 +1357,20 @@ hipError_t launch_sh_eval(const Camera& cam, const GaussIn& g, GeomPtrs geo, hip
 // definition the mapping step and the SH-stage colour step share, with no FP contraction (each
 // operation rounded, like torch's separate kernels): the two kernels had contracted differently and
 // diverged by an ulp from the second step on.
-// Streams read or written once per iteration (optimizer parameters and moments, SH coefficients): with
-// GSR_NT_STREAMS the loads and stores carry the nontemporal hint (the guide's streaming form: tools/micro/stream
-// measures 6.33 TB/s for nontemporal float4 copies against 5.77 TB/s plain); the values are the same bits.
-#ifndef GSR_NT_STREAMS
-#define GSR_NT_STREAMS 1  // (config-4 mapping: sh_bwd 231 -> 204, map_transform_bwd 90 -> 67, sh_eval 69 -> 36 us)
-#endif
+// Streams read or written once per iteration (optimizer parameters and moments, SH coefficients): the loads and
+// stores carry the nontemporal hint (the guide's streaming form: tools/micro/stream measures 6.33 TB/s for
+// nontemporal float4 copies against 5.77 TB/s plain); the values are the same bits.  Against plain accesses at
+// config-4 mapping: sh_bwd 231 -> 204, map_transform_bwd 90 -> 67, sh_eval 69 -> 36 us.
 typedef float gsr_f4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float ld_stream(const float* p) {
-    if constexpr (GSR_NT_STREAMS != 0) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-__device__ __forceinline__ void st_stream(float* p, float v) {
-    if constexpr (GSR_NT_STREAMS != 0) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
+__device__ __forceinline__ float ld_stream(const float* p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ void st_stream(float* p, float v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ float4 ld_stream(const float4* p) {
-    if constexpr (GSR_NT_STREAMS != 0) {
-        const gsr_f4v v = __builtin_nontemporal_load(reinterpret_cast<const gsr_f4v*>(p));
-        return make_float4(v.x, v.y, v.z, v.w);
-    } else {
-        return *p;
-    }
+    const gsr_f4v v = __builtin_nontemporal_load(reinterpret_cast<const gsr_f4v*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void st_stream(float4* p, float4 v) {
-    if constexpr (GSR_NT_STREAMS != 0) {
-        const gsr_f4v w = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(w, reinterpret_cast<gsr_f4v*>(p));
-    } else {
-        *p = v;
-    }
+    const gsr_f4v w = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(w, reinterpret_cast<gsr_f4v*>(p));
 }
 
 __device__ __forceinline__ float adam_update_elem(float p, float g, float& m, float& v, float ss, float w1, float beta2,

@@ -2,7 +2,7 @@
 //
 // The kernels call the hooks of one RenderDiag object at their phase boundaries; each hook is an empty
 // inline function unless its diagnostics build switch is set (the build_variant libraries that
-// tools/stepstat.py, tools/phase_bwd.py and tools/wgtime.py load through GSR_LIB):
+// tools/stepstat.py, tools/phase.py and tools/wgtime.py load through GSR_LIB):
 //   GSR_STEPSTAT  render_bwd step statistics: [wave-steps, wave-steps with a contributing pair,
 //                 contributing (lane, entry) pairs, pad (lane, entry) slots, batches x waves,
 //                 listed (row, entry) items, listed items with no contributing pixel]
@@ -10,8 +10,12 @@
 //                 [2] row / slot list build, [3] row walk, [4] barrier after the walk, [5] entry totals +
 //                 record stores, [6] barrier after the totals, [7] batches x waves
 //   GSR_WGTIME    per-workgroup [start, end, HW_ID, XCC_ID] of the render kernels (gsr_common.h)
-// GSR_ABLATE / GSR_FWD_ABLATE (timing ablations, results invalid) are compile-time constants read through
-// kAblate / kFwdAblate.
+//   GSR_ABLATE / GSR_FWD_ABLATE  timing ablations of the backward / forward render (results invalid);
+//                 GSR_ABLATE is read through kAblate
+//   GSR_DUP_PHASE one render phase run twice, for a VALU census by SQ counters (results unchanged)
+// These and RenderDiag are the only build switches of the kernels: the numeric tunables (GSR_BWD_BB ...) fork
+// no code, and an A/B of two implementations is built from two revisions (build.build_from_rev), not from a
+// macro in the sources.
 #pragma once
 #include "gsr_common.h"
 
@@ -24,6 +28,11 @@
 #ifndef GSR_ABLATE
 #define GSR_ABLATE 0  // render_bwd / gauss_bwd timing ablations (1 no row reduction, 2 no entry totals, 3-5 pose tail,
                       // 6 no tracking-loss arrival / sum)
+#endif
+#ifndef GSR_FWD_ABLATE
+#define GSR_FWD_ABLATE 0  // timing ablations (tools/gpu_round.sh ab=; results invalid except 5, 6): 1 no per-tile
+                          // sort, 2 no walk, 4 no tracking-loss epilogue, 5 bounding-box block masks, 6 no block
+                          // masks, 7 masks of an earlier launch read back, 8 no image stores.  0 in every real build
 #endif
 
 namespace gsr {

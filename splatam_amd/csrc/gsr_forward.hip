@@ -16,13 +16,7 @@
 #include "gsr_diag.h"
 #include "gsr_render_fwd.h"
 
-#ifndef GSR_CULL_TAIL
-#define GSR_CULL_TAIL 1  // culled instances written to point_list's tail (0: timing experiments only)
-#endif
-
 namespace gsr {
-
-constexpr bool kCullTail = GSR_CULL_TAIL != 0;
 
 
 // ------------------------------------------------------------- preprocess --
@@ -174,11 +168,9 @@ preprocess_kernel(Camera cam, GaussIn g, GeomPtrs geo, int* radii, uint32_t* __r
                     live = 0u;
                     for (int ty = y0, k = 0; ty < y1; ty++)
                         for (int tx = x0; tx < x1; tx++, k++)
-                            live |= (GSR_CULL_EXACT ? mask_of_geom(mg, (float)(tx * TILE_X), (float)(ty * TILE_Y)) != 0u
-                                                    : tile_reached(mg, (float)(tx * TILE_X), (float)(ty * TILE_Y)))
-                                        ? 1u << k : 0u;
+                            live |= tile_reached(mg, (float)(tx * TILE_X), (float)(ty * TILE_Y)) ? 1u << k : 0u;
                 }
-                if constexpr (kCullTail && EXACT) culled = culled_below(live, tiles);
+                if constexpr (EXACT) culled = culled_below(live, tiles);
                 geo.bin[i] = make_uint4(rlo, rhi, __float_as_uint(pv.z), live);
                 if (!g.sh_staged && !g.colors) geo.clamp[i] = clamped;  // (read only by the SH backward)
                 for (int ty = y0, k = 0; ty < y1; ty++)  // per-tile instance counts -> bucket ranges
@@ -206,7 +198,7 @@ preprocess_kernel(Camera cam, GaussIn g, GeomPtrs geo, int* radii, uint32_t* __r
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     uint32_t incl = wave_incl_scan(tiles);
     if (lane == 63) wsum[wv] = incl;
-    if constexpr (kCullTail && EXACT) {  // the workgroup's culled instances (the exact tail, duplicate)
+    if constexpr (EXACT) {  // the workgroup's culled instances (the exact tail, duplicate)
         const uint32_t cincl = wave_incl_scan(culled);
         if (lane == 63) wcul[wv] = cincl;
     }
@@ -227,7 +219,7 @@ preprocess_kernel(Camera cam, GaussIn g, GeomPtrs geo, int* radii, uint32_t* __r
     const bool viol = __syncthreads_or(violation);
     if (threadIdx.x == blockDim.x - 1) {
         geo.wgsum[blockIdx.x] = (woff + incl) | (viol ? 0x80000000u : 0u);
-        if constexpr (kCullTail && EXACT) {
+        if constexpr (EXACT) {
             uint32_t cw = 0;
             for (int k = 0; k < (int)(blockDim.x >> 6); k++) cw += wcul[k];
             geo.wgcull[blockIdx.x] = cw;
@@ -697,9 +689,6 @@ constexpr int DUP_T = 512;
 #ifndef GSR_DUP_LOOP_MAX
 #define GSR_DUP_LOOP_MAX 16  // rows whose Gaussians touch at most this many tiles place instances per lane
 #endif
-#ifndef GSR_NO_PLAN
-#define GSR_NO_PLAN 0  // timing experiment: row-major render order instead of tile_plan
-#endif
 // the snapshot the host reads after the duplicate (Camera::host_snap): two 16-B vector stores to the coherent
 // pinned buffer, made visible to the host by the kernel's end-of-kernel release
 __device__ __forceinline__ void store_host_snap(uint32_t* snap, uint4 lo, uint4 hi) {
@@ -730,7 +719,6 @@ __device__ __forceinline__ void duplicate_bucket_body(Camera cam, int P, GeomPtr
     //   else (static mode: the library is the only reader): padding -- slot u of the tail holds the Gaussian
     //     owning rect instance slot u (offsets[i] <= u < offsets[i] + tiles[i]), which needs no global prefix of
     //     the culled counts (that bookkeeping cost the kernel 16 VGPRs and a second dispatch round).
-    constexpr bool TAIL = kCullTail;
     constexpr int ROW = DUP_G * DUP_T;  // Gaussians per count-matrix row (1 << cam.pre_shift)
     __shared__ uint32_t s_incl[ROW];
     __shared__ uint32_t s_x0[ROW], s_y0[ROW], s_w[ROW], s_depth[ROW], s_live[ROW];
@@ -774,11 +762,11 @@ __device__ __forceinline__ void duplicate_bucket_body(Camera cam, int P, GeomPtr
             const uint32_t k2 = k + DUP_T;
             const uint32_t v = geo.wgsum[k], v2 = k2 < nb ? geo.wgsum[k2] : 0u;
             // (EXACT: preprocess wrote wgcull; loaded unconditionally, with the workgroup sums)
-            const uint32_t c = (TAIL && EXACT) ? geo.wgcull[k] : 0u, c2 = (TAIL && EXACT && k2 < nb) ? geo.wgcull[k2] : 0u;
+            const uint32_t c = EXACT ? geo.wgcull[k] : 0u, c2 = (EXACT && k2 < nb) ? geo.wgcull[k2] : 0u;
             viol |= (v | v2) >> 31;
             all += (v & 0x7fffffffu) + (v2 & 0x7fffffffu);
             pre += (k < b ? (v & 0x7fffffffu) : 0u) + (k2 < b ? (v2 & 0x7fffffffu) : 0u);
-            if (TAIL && EXACT) {
+            if (EXACT) {
                 call += c + c2;
                 cpre += (k < b ? c : 0u) + (k2 < b ? c2 : 0u);
             }
@@ -803,7 +791,7 @@ __device__ __forceinline__ void duplicate_bucket_body(Camera cam, int P, GeomPtr
         all = wave_sum_u32(all);
         viol = wave_max_u32(viol);
         vmax = wave_max_u32(vmax);
-        if (TAIL && EXACT && cam.cull) {
+        if (EXACT && cam.cull) {
             cpre = wave_sum_u32(cpre);
             call = wave_sum_u32(call);
         }
@@ -812,7 +800,7 @@ __device__ __forceinline__ void duplicate_bucket_body(Camera cam, int P, GeomPtr
             s_red[1][w] = all;
             s_red[2][w] = viol;
             s_red[3][w] = vmax;
-            if (TAIL && EXACT) {
+            if (EXACT) {
                 s_cred[0][w] = cpre;
                 s_cred[1][w] = call;
             }
@@ -828,14 +816,14 @@ __device__ __forceinline__ void duplicate_bucket_body(Camera cam, int P, GeomPtr
             viol |= s_red[2][k];
             vmax = max(vmax, s_red[3][k]);
             woff += k < w ? s_red[4][k] : 0u;
-            if (TAIL && !EXACT) lsum += s_red[4][k];
-            if (TAIL && EXACT) {
+            if (!EXACT) lsum += s_red[4][k];
+            if (EXACT) {
                 cpre += s_cred[0][k];
                 call += s_cred[1][k];
             }
         }
-        if (TAIL && EXACT) ctail = all - call + cpre;  // this workgroup's first culled instance in point_list
-        if (TAIL && !EXACT) ltot = lsum;
+        if (EXACT) ctail = all - call + cpre;  // this workgroup's first culled instance in point_list
+        if (!EXACT) ltot = lsum;
         uint32_t run = woff + cincl - csum;  // bucket start of this thread's first tile
         if (in_regs) {
 #pragma unroll
@@ -868,23 +856,19 @@ __device__ __forceinline__ void duplicate_bucket_body(Camera cam, int P, GeomPtr
             }
         }
         if (b == 0 && cam.tile_order_out) {
-#if GSR_NO_PLAN
-            for (int u = tid; u < ntiles; u += DUP_T) cam.tile_order_out[u] = (uint32_t)u;
-#else
             __shared__ uint32_t s_plan[PLAN_BUCKETS];
             if (in_regs)
                 tile_plan<DUP_T, TPT>(tot, ntiles, cam.sched_cus, cam.tile_order_out, s_plan, wsum, tv, t0, t1);
             else
                 tile_plan<DUP_T>(tot, ntiles, cam.sched_cus, cam.tile_order_out, s_plan, wsum);
-#endif
         }
         base = pre;
         if (all > guard.cap_inst || vmax > guard.cap_tile) return;  // workgroup-uniform
     } else {
         if (guard.overflow()) return;
         base = geo.blocksums[blockIdx.x];
-        if (TAIL && !EXACT && ntiles > 0) ltot = ranges[ntiles - 1].y;  // (the scan launch wrote the ranges)
-        if (TAIL && EXACT && cam.cull) {  // (the global-atomic path, > MAX_LDS_TILES tiles) the culled totals' prefix
+        if (!EXACT && ntiles > 0) ltot = ranges[ntiles - 1].y;  // (the scan launch wrote the ranges)
+        if (EXACT && cam.cull) {  // (the global-atomic path, > MAX_LDS_TILES tiles) the culled totals' prefix
             const uint32_t b = blockIdx.x, nb = gridDim.x;
             uint32_t cpre = 0, call = 0;
             for (uint32_t k = tid; k < nb; k += DUP_T) {
@@ -913,7 +897,7 @@ __device__ __forceinline__ void duplicate_bucket_body(Camera cam, int P, GeomPtr
     for (int g = 0; g < DUP_G; g++) {
         tsum += t[g];
         tmax = max(tmax, t[g]);
-        cg[g] = (TAIL && EXACT && cam.cull && t[g]) ? culled_below(r[g].w, t[g]) : 0u;
+        cg[g] = (EXACT && cam.cull && t[g]) ? culled_below(r[g].w, t[g]) : 0u;
         csum += cg[g];
         const int q = DUP_G * tid + g;
         if (t[g]) {
@@ -925,19 +909,19 @@ __device__ __forceinline__ void duplicate_bucket_body(Camera cam, int P, GeomPtr
         }
     }
     uint32_t incl = wave_incl_scan(tsum);
-    const uint32_t cincl = (TAIL && EXACT && cam.cull) ? wave_incl_scan(csum) : 0u;
+    const uint32_t cincl = (EXACT && cam.cull) ? wave_incl_scan(csum) : 0u;
     tmax = wave_max_u32(tmax);
     __syncthreads();  // (wsum is also tile_plan's scratch)
     if (lane == 63) {
         wsum[w] = incl;
-        if (TAIL && EXACT) s_cws[w] = cincl;
+        if (EXACT) s_cws[w] = cincl;
     }
     if (lane == 0) s_tmax[w] = tmax;
     __syncthreads();
     uint32_t run = incl - tsum, crun = ctail + cincl - csum;
     for (int k = 0; k < w; k++) {
         run += wsum[k];
-        if (TAIL && EXACT) crun += s_cws[k];
+        if (EXACT) crun += s_cws[k];
     }
 #pragma unroll
     for (int k = 0; k < DUP_T / 64; k++) tmax = max(tmax, s_tmax[k]);
@@ -946,12 +930,12 @@ __device__ __forceinline__ void duplicate_bucket_body(Camera cam, int P, GeomPtr
     for (int g = 0; g < DUP_G; g++) {  // Gaussian order: the workgroup-local instance offsets of preprocess
         const uint32_t off = base + run;
         if (i0 + g < P) geo.offsets[i0 + g] = off;
-        if (TAIL && !EXACT && off + t[g] > ltot)  // padding tail: the owner of each rect slot >= L
+        if (!EXACT && off + t[g] > ltot)  // padding tail: the owner of each rect slot >= L
             for (uint32_t u = max(off, ltot); u < off + t[g]; u++) point_list[u] = (uint64_t)(i0 + g);
         run += t[g];
         s_incl[DUP_G * tid + g] = run;
         cx[g] = crun;
-        if (TAIL && EXACT) s_cx[DUP_G * tid + g] = crun;  // (read by the load-balanced path)
+        if (EXACT) s_cx[DUP_G * tid + g] = crun;  // (read by the load-balanced path)
         crun += cg[g];
     }
     if (tmax <= (uint32_t)GSR_DUP_LOOP_MAX) {
@@ -967,7 +951,7 @@ __device__ __forceinline__ void duplicate_bucket_body(Camera cam, int P, GeomPtr
             uint32_t ct = cx[g];
             for (uint32_t k = 0; k < t[g]; k++) {
                 if (!tile_live(r[g].w, k)) {  // culled (Camera::cull): not in the bucket (EXACT: in the tail)
-                    if (TAIL && EXACT) point_list[ct++] = (uint64_t)gi;
+                    if (EXACT) point_list[ct++] = (uint64_t)gi;
                     continue;
                 }
                 const uint32_t tile = (y0 + k / wdt) * (uint32_t)cam.gx + x0 + k % wdt;
@@ -988,7 +972,7 @@ __device__ __forceinline__ void duplicate_bucket_body(Camera cam, int P, GeomPtr
         }
         const uint32_t local = e - ((lo == 0) ? 0u : s_incl[lo - 1]);
         if (!tile_live(s_live[lo], local)) {  // culled (Camera::cull): not in the bucket (EXACT: in the tail)
-            if (TAIL && EXACT)
+            if (EXACT)
                 point_list[s_cx[lo] + culled_below(s_live[lo], local)] = (uint64_t)(blockIdx.x * ROW + lo);
             continue;
         }

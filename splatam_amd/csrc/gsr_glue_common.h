@@ -131,14 +131,12 @@ __device__ __forceinline__ void track_xform_compute(const TrackXf& x, const Pose
 __device__ __forceinline__ void track_xform_store(int i, const float (&m)[3], float4 q, const float (&c2)[3], float op,
                                                   const float (&s)[3], float* mc, float* rot, float* dcol,
                                                   float* opac, float* scl) {
-#ifndef GSR_XF_NOSTORE
     mc[3 * i] = m[0]; mc[3 * i + 1] = m[1]; mc[3 * i + 2] = m[2];
     rot[4 * i] = q.x; rot[4 * i + 1] = q.y; rot[4 * i + 2] = q.z; rot[4 * i + 3] = q.w;
     dcol[3 * i] = c2[0]; dcol[3 * i + 1] = c2[1]; dcol[3 * i + 2] = c2[2];
     opac[i] = op;
 #pragma unroll
     for (int k = 0; k < 3; k++) scl[3 * i + k] = s[k];
-#endif
 }
 
 // Forward-state check of the fused optimizer steps: `st` is a forward's device counters or
@@ -186,21 +184,14 @@ __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& 
 // beta^n for the Adam bias corrections, formed in double like torch's python floats: by
 // squaring (n = the step count, an integer; within a few double ulps of pow(), so the float
 // scalars derived from it are the same) -- 1 us faster than the device pow() on the one thread
-// that runs the pose step (GSR_POW_INT=0: pow())
-#ifndef GSR_POW_INT
-#define GSR_POW_INT 1
-#endif
+// that runs the pose step
 __device__ __forceinline__ double adam_pow(double b, float step) {
-#if GSR_POW_INT
     double r = 1.0;
     for (unsigned n = (unsigned)step; n; n >>= 1) {
         if (n & 1u) r *= b;
         b *= b;
     }
     return r;
-#else
-    return pow(b, (double)step);
-#endif
 }
 
 // The pose chain on the 16 summed terms S: dR -> dn (build_rotation) -> dc

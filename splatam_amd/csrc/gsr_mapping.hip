@@ -375,9 +375,6 @@ __global__ void __launch_bounds__(ADAM_BLOCK) adam_step_kernel(AdamArgs a) {
 }
 
 // ---------------------------------------------------- mapping transform bwd --
-#ifndef GSR_NT_GRADS
-#define GSR_NT_GRADS 1  // (config 4: map_transform_bwd 66.5 -> 61.8 us, profiles/r9z_ab_nt_grads.txt)
-#endif
 struct MapAdam {  // the mapping optimizer's state, applied in place (NULL p: write gradients instead)
     float* p[5];          // means3D, unnorm_rotations, logit_opacities, log_scales, colours
     float* m[5];
@@ -455,8 +452,9 @@ map_transform_bwd_kernel(int P, const float* ur, const float* lo, const float* l
     }
     if (i >= P) return;
     const Pose ps = make_pose(cq, nullptr, qs);
-    // (the incoming gradients and camera-frame means are read once: GSR_NT_GRADS streams them nontemporally)
-    auto ldg = [](const float* q) { return GSR_NT_GRADS ? ld_stream(q) : *q; };
+    // (the incoming gradients and camera-frame means are read once, so streamed nontemporally: map_transform_bwd
+    // 66.5 -> 61.8 us at config 4 against plain loads, profiles/r9z_ab_nt_grads.txt)
+    auto ldg = [](const float* q) { return ld_stream(q); };
     float g0 = gm ? ldg(gm + 3 * i) : 0.f, g1 = gm ? ldg(gm + 3 * i + 1) : 0.f, g2 = gm ? ldg(gm + 3 * i + 2) : 0.f;
     if (gd) {  // colours [z, 1, z^2]: dz = dc0 + 2 z dc2
         const float z = w2c[8] * ldg(mc + 3 * i) + w2c[9] * ldg(mc + 3 * i + 1) + w2c[10] * ldg(mc + 3 * i + 2) + w2c[11];

@@ -25,17 +25,13 @@ constexpr uint32_t TILE_SORT_REGS = 1024;  // longest list sorted in registers (
 // (the runtime-loop ds_bpermute version spent most of its time in SALU/branch
 // overhead and LDS-permute latency: 32 us on the config-3 buckets,
 // tools/micro/sort_bench.hip).  Lane mappings checked by tools/micro/lane_xor.hip.
-#ifndef GSR_SORT_SWIZZLE
-#define GSR_SORT_SWIZZLE 0  // lane exchanges of distance <= 16 by ds_swizzle (LDS pipe) instead of DPP / permlane (VALU):
-                            // 779 static VALU fewer, bitwise the same order, the fused kernel unchanged (r8s_ab_sort_swizzle)
-#endif
+// (The exchanges of distance <= 16 by ds_swizzle -- the LDS pipe instead of the VALU -- were 779 static VALU
+// fewer in render_track, bitwise the same order, and left the fused kernel's time unchanged:
+// profiles/r8s_ab_sort_swizzle.txt.)
 template <int M>
 __device__ __forceinline__ uint32_t lane_xor(uint32_t x) {
     static_assert(M == 1 || M == 2 || M == 4 || M == 8 || M == 16 || M == 32, "lane xor distance");
-    if constexpr (GSR_SORT_SWIZZLE && M <= 16) {
-        // bit-mode swizzle inside each 32-lane half: lane' = (lane & 0x1F) ^ M
-        return (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, (M << 10) | 0x1F);
-    } else if constexpr (M == 1) {
+    if constexpr (M == 1) {
         return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
     } else if constexpr (M == 2) {
         return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xF, 0xF, false);  // quad_perm [2,3,0,1]
@@ -128,17 +124,6 @@ __device__ void tile_sort_regs(const uint64_t* __restrict__ src, uint32_t cnt, E
 //                for every other chunk (staged in LDS), the number of that chunk's
 //                keys below it -- exact, as the keys are unique in a tile.
 // The result equals a stable (tile, depth) radix order (ids break depth ties).
-#ifndef GSR_FWD_PAIR25
-#define GSR_FWD_PAIR25 1  // dual forward walk: channels 2 and 5 blended by one v_pk_fma (0: two v_fmac)
-#endif
-#ifndef GSR_FWD_DONE_EXIT
-#define GSR_FWD_DONE_EXIT 1  // forward walk: done lanes exit the loop (0: a wave-uniform ballot test per step)
-#endif
-#ifndef GSR_FWD_ABLATE
-#define GSR_FWD_ABLATE 0  // timing ablations (tools/gpu_round.sh ab=; results invalid except 5, 6): 1 no per-tile
-                          // sort, 2 no walk, 4 no tracking-loss epilogue, 5 bounding-box block masks, 6 no block
-                          // masks, 7 masks of an earlier launch read back, 8 no image stores.  0 in every real build
-#endif
 #if GSR_FWD_ABLATE == 7
 static __device__ uint16_t g_fab_mask[1u << 23];
 #endif
@@ -324,7 +309,7 @@ __device__ __forceinline__ FwdPix fwd_tile(const Camera& cam, int tile, const ui
             s_b[tid] = pb;
             // (DUAL: the second set's third channel rides in s_c.w -- the walk blends channels (0, 1), (2, 5)
             // and (3, 4) as three pairs -- and the rect half it replaces is not read after staging)
-            s_c[tid] = (DUAL && GSR_FWD_PAIR25) ? make_float4(pc.x, pc.y, pc.z, pd.z) : pc;
+            s_c[tid] = DUAL ? make_float4(pc.x, pc.y, pc.z, pd.z) : pc;
             if (DUAL) s_d[tid] = pd;
             s_mask[tid] = (uint16_t)pm;
             ent = ((PointEntry)pm << 32) | pg;  // the mask, for render_bwd (stored below)
@@ -349,8 +334,9 @@ __device__ __forceinline__ FwdPix fwd_tile(const Camera& cam, int tile, const ui
         dg.phase(2);
         for (int i = 0; i < (GSR_FWD_ABLATE == 2 ? 0 : n); i += 4) {
             // a lane whose pixel is done leaves the walk (the wave's loop ends when every lane has: exec-mask
-            // bookkeeping on the scalar unit -- a __ballot(!done) test cost 2 VALU per step)
-            if (GSR_FWD_DONE_EXIT ? done : __ballot(!done) == 0ull) break;
+            // bookkeeping on the scalar unit -- a wave-uniform __ballot(!done) test cost 2 VALU per step, 87
+            // against 85, and render_track 97.6-97.9 against 97.0-97.5 us: profiles/r7q_ab_fwd_done_exit.txt)
+            if (done) break;
             int jb[4];  // byte offsets 16 j, one ds_read_u16 each (no unpacking on the VALU; volatile keeps
 #pragma unroll  // the four adjacent u16 loads from being merged into one b64 load + 4 VALU unpacks)
             for (int k = 0; k < 4; k++)
@@ -386,17 +372,15 @@ __device__ __forceinline__ FwdPix fwd_tile(const Camera& cam, int tile, const ui
                 if (blend) {
                     const float wgt = alpha[k] * T;
                     C01 = __builtin_elementwise_fma(v2f{c.x, c.y}, v2f{wgt, wgt}, C01);
-                    if (DUAL && GSR_FWD_PAIR25) {  // the same fused products per channel, two per instruction
+                    if (DUAL) {  // channels 2 and 5 by one v_pk_fma_f32: the same fused products as two v_fmac,
+                        // 81 against 85 VALU per step, render_track 95.8-96.1 against 97.3-97.4 us
+                        // (profiles/r7z_ab_fwd_pair25.txt)
                         const v2f c25 = __builtin_elementwise_fma(v2f{c.z, c.w}, v2f{wgt, wgt}, v2f{C2, C5});
                         C2 = c25.x;
                         C5 = c25.y;
                         C34 = __builtin_elementwise_fma(v2f{c2.x, c2.y}, v2f{wgt, wgt}, C34);
                     } else {
                         C2 += c.z * wgt;
-                        if (DUAL) {
-                            C34 = __builtin_elementwise_fma(v2f{c2.x, c2.y}, v2f{wgt, wgt}, C34);
-                            C5 += c2.z * wgt;
-                        }
                     }
                     if (T > 0.5f && test_T < 0.5f) D = depth[k];  // median depth (forward.cu:368-372)
                     T = test_T;
@@ -413,9 +397,6 @@ __device__ __forceinline__ FwdPix fwd_tile(const Camera& cam, int tile, const ui
 }
 
 
-#ifndef GSR_NT_STORES
-#define GSR_NT_STORES 0  // render kernels' record / image stores as non-temporal (streaming) stores
-#endif
 #ifndef GSR_L1_CH
 #define GSR_L1_CH 8  // tracking-loss epilogue: partials in flight per round trip of the last workgroup
 #endif
@@ -494,13 +475,12 @@ __device__ __forceinline__ void fwd_epilogue(const Camera& cam, int tile, const 
     if (inside && final_T != nullptr && (GSR_FWD_ABLATE != 8 || T == 1.2345f)) {  // (ablation 8: no image stores)
         const int pid = py * cam.W + px;
         const int HW = cam.W * cam.H;
-        auto st = [](float* p, float v) {
-            if (GSR_NT_STORES) __builtin_nontemporal_store(v, p);
-            else *p = v;
-        };
+        // plain stores (streaming stores measured neutral, profiles/r4l_ab_nt.txt), through a pointer without
+        // the parameters' __restrict__: stored through the parameters themselves the epilogue is scheduled
+        // differently, which has not been measured
+        auto st = [](float* p, float v) { *p = v; };
         st(final_T + pid, T);
-        if (GSR_NT_STORES) __builtin_nontemporal_store(last16 >> 4, n_contrib + pid);
-        else n_contrib[pid] = last16 >> 4;
+        n_contrib[pid] = last16 >> 4;
         st(out_color + pid, C0 + T * cam.bg[0]);
         st(out_color + HW + pid, C1 + T * cam.bg[1]);
         st(out_color + 2 * HW + pid, C2 + T * cam.bg[2]);

@@ -20,13 +20,7 @@ namespace gsr {
 namespace {
 
 constexpr int SH_BLOCK = 256;
-#ifndef GSR_SH_SPLIT
-#define GSR_SH_SPLIT 1  // sh_bwd_split_kernel for the fused colour Adam step (config 4: 205 -> 195 us)
-#endif
 constexpr int SH_SPLIT_BLOCK = 128;
-#ifndef GSR_SH_BWD_NT
-#define GSR_SH_BWD_NT 0  // sh_bwd's coefficient staging with nontemporal loads (its Adam step re-reads them)
-#endif
 // sh_eval: one wave per workgroup (12.5 KB of LDS at D = 3): the waves of a CU stage and evaluate
 // independently instead of in barrier-coupled groups of four
 
@@ -115,7 +109,7 @@ __device__ __forceinline__ void adam_rows(float* p, float* m, float* v, const fl
             float4 pv[U], mv[U], vv[U];
 #pragma unroll
             for (int u = 0; u < U; u++) {
-                pv[u] = GSR_SH_BWD_NT ? ld_stream(p4 + e4 + u * SH_BLOCK) : p4[e4 + u * SH_BLOCK];
+                pv[u] = p4[e4 + u * SH_BLOCK];  // (plain: the coefficients the staging just read)
                 mv[u] = ld_stream(m4 + e4 + u * SH_BLOCK);
                 vv[u] = ld_stream(v4 + e4 + u * SH_BLOCK);
             }
@@ -250,7 +244,7 @@ sh_bwd_kernel(Camera cam, GaussIn g, GeomPtrs geo, const int* __restrict__ radii
     __shared__ float s_sh[SH_BLOCK * T::PITCH];
     const int base = blockIdx.x * SH_BLOCK;
     const int n = min(SH_BLOCK, g.P - base);
-    stage_rows<NSH, SH_BLOCK, GSR_SH_BWD_NT != 0>(s_sh, g.shs + (size_t)T::ROW * base, n);
+    stage_rows<NSH, SH_BLOCK>(s_sh, g.shs + (size_t)T::ROW * base, n);
     __syncthreads();
     if ((int)threadIdx.x < n) {
         const int i = base + threadIdx.x;
@@ -342,7 +336,9 @@ hipError_t launch_sh_bwd_t(const Camera& cam, const GaussIn& g, GeomPtrs geo, co
     using T = ShTile<NSH>;
     const bool aligned = ((reinterpret_cast<uintptr_t>(g.shs) | reinterpret_cast<uintptr_t>(sa.m) |
                            reinterpret_cast<uintptr_t>(sa.v)) & 15u) == 0;
-    if (GSR_SH_SPLIT && sa.m && T::ROW % 4 == 0 && aligned) {  // (the float4 form of adam_rows_lds)
+    // the fused colour Adam step goes through sh_bwd_split_kernel (the float4 form of adam_rows_lds): 205 -> 195 us
+    // at config 4 against sh_bwd_kernel's own step
+    if (sa.m && T::ROW % 4 == 0 && aligned) {
         hipLaunchKernelGGL(sh_bwd_split_kernel<NSH>, dim3((g.P + SH_SPLIT_BLOCK - 1) / SH_SPLIT_BLOCK),
                            dim3(SH_SPLIT_BLOCK), 0, s, cam, g, geo, radii, drgb, dmeans3D, dsh, guard, sa);
         return hipGetLastError();
