@@ -9,8 +9,11 @@ autograd:
 * alpha = min(0.99, o*G): the backward never zeroes the gradient at the 0.99
   clamp (backward.cu:974-1038) -> straight-through estimator here;
 * the +-1.3 tanfov clamp of t.x / t.y: backward.cu:175-176,262-264 zeroes the
-  x/y gradient and treats the clamped value as a constant in dJ/dt_z;
-* dL/dscale is taken w.r.t. (scale_modifier * scale) (backward.cu:457-459).
+  x/y gradient and treats the clamped value as a constant in dJ/dt_z.
+
+One convention is left to the caller: the reference takes dL/dscale w.r.t. (scale_modifier * scale)
+(backward.cu:457-459), while autograd through `scales` here is the gradient w.r.t. the scale itself,
+scale_modifier times larger -- divide it by scale_modifier before comparing.
 
 The per-tile candidate lists, depth order and the discrete decisions (skip,
 early termination) come from the float64 oracle run on the same inputs.
