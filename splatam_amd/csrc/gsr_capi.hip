@@ -758,14 +758,17 @@ struct Backward {
         // pre_inst: the records were formed by the fused tracking render (render_track_kernel)
         const size_t rec_bytes =
             (c.pre_inst || R <= 0) ? 0 : align_up(sizeof(float) * rec.stride * (size_t)R, 256);
-        const size_t scratch_bytes = rec_bytes + (shs_staged ? sizeof(float) * 3 * (size_t)P : 0);
+        // (a caller who asked for dL/dcolor with SH input gets it, as from the per-lane chain: gauss_bwd then
+        // writes it straight into the caller's array, sh_bwd reads it from there and no scratch copy is reserved)
+        const bool own_drgb = shs_staged && !out.dcolors;
+        const size_t scratch_bytes = rec_bytes + (own_drgb ? sizeof(float) * 3 * (size_t)P : 0);
         char* scratch = nullptr;
         if (scratch_bytes > 0) {
             if (!c.alloc) return fail(GSR_ERR_INVALID_ARG, "allocator callback required");
             if (int rc = obtain(c.alloc, c.alloc_ctx, GSR_BUF_SCRATCH, scratch_bytes, "backward scratch", &scratch))
                 return rc;
         }
-        float* drgb = shs_staged ? (float*)(scratch + rec_bytes) : nullptr;
+        float* drgb = !shs_staged ? nullptr : own_drgb ? (float*)(scratch + rec_bytes) : out.dcolors;
         float* inst = nullptr;
         hipError_t e;
         if (c.pre_inst) {
