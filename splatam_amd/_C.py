@@ -18,6 +18,7 @@ import ctypes
 import os
 import threading
 import weakref
+from typing import NamedTuple
 
 import torch
 
@@ -160,6 +161,85 @@ def _gaussians(means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, d
                      opacities=_ptr(keep[3]), scales=_ptr(keep[4]), rotations=_ptr(keep[5]),
                      cov3D_precomp=_ptr(keep[6]))
     return g, keep, M
+
+
+class TrackXform(NamedTuple):
+    """The transform a static forward forms inside its preprocess: gsr_track_xform (include/gsr_glue.h) by field,
+    as the tensors and addresses it is filled from (`xform_struct`).  The forward's means3D, colors2, opacity,
+    scales and rotations arguments are then the transform's OUTPUTS: preallocated contiguous float32, written when
+    store_rendervars is true (the mapping forward refuses anything else).  Built by glue.map_transform(defer=...)
+    and glue.tracking_iteration; read by rasterize_gaussians_dual(xform=) and track_forward_dual_static(xform=)."""
+    means_world: torch.Tensor
+    unnorm_rot: torch.Tensor
+    logit_opac: torch.Tensor
+    log_scales: torch.Tensor
+    scale_cols: int
+    cam_q: int        # address of the pose column's quaternion (stride q_stride floats) ...
+    cam_t: int        # ... and of its translation
+    q_stride: int
+    w2c: torch.Tensor
+    store_rendervars: bool = True
+    alive: torch.Tensor | None = None  # uint8 [P], 0 = culled
+    keep: tuple = ()  # the tensors cam_q / cam_t point into: alive as long as the record is
+
+
+def xform_struct(x: TrackXform) -> GsrTrackXform:
+    return GsrTrackXform(means_world=x.means_world.data_ptr(), unnorm_rot=x.unnorm_rot.data_ptr(),
+                         logit_opac=x.logit_opac.data_ptr(), log_scales=x.log_scales.data_ptr(),
+                         scale_cols=int(x.scale_cols), cam_q=x.cam_q, cam_t=x.cam_t, q_stride=int(x.q_stride),
+                         w2c=x.w2c.data_ptr(), store_rendervars=int(bool(x.store_rendervars)), alive=_ptr(x.alive))
+
+
+def _check_status(status, device):
+    if status is None or status.device != device or status.numel() < 4:
+        raise RuntimeError("a static forward needs a device status tensor of 4 int32")
+
+
+def _check_alive(alive, P, device):
+    if alive is not None and (alive.device != device or alive.dtype != torch.uint8 or alive.numel() != P or
+                              not alive.is_contiguous()):
+        raise RuntimeError("alive must be a contiguous uint8 tensor of P entries on the render device")
+
+
+def _check_xform_outputs(device, *outs):
+    if any(t is None or not t.is_contiguous() or t.dtype != torch.float32 or t.device != device for t in outs):
+        raise RuntimeError("a forward with xform writes means3D, colors2, opacity, scales and rotations: they must "
+                           "be contiguous float32 tensors on the device")
+
+
+def _settings_of(st, prefiltered):
+    """_settings' leading arguments from a GaussianRasterizationSettings."""
+    return (st.bg, st.viewmatrix, st.projmatrix, st.campos, st.tanfovx, st.tanfovy, int(st.image_height),
+            int(st.image_width), st.scale_modifier, st.sh_degree, prefiltered)
+
+
+def _forward_state(R, geomBuffer, binningBuffer, imageBuffer):
+    """The backwards' (num_rendered, geometry, binning, image) segment: what their forward returned."""
+    return (int(R), geomBuffer.data_ptr(), binningBuffer.data_ptr() if binningBuffer.numel() else None,
+            imageBuffer.data_ptr())
+
+
+class _Frame:
+    """What the dual and tracking entry points share around their one library call: the settings and Gaussians
+    structs (their tensors kept alive here), then per call a fresh allocator state, the call itself --
+    fn(settings, gaussians, *middle, allocator, NULL, stream) -- its error check and the buffers it allocated.
+    A family's variants differ in `fn` and in the segments of `middle`; a new variant's argument goes into the
+    segment it belongs to, once."""
+
+    def __init__(self, device, settings, gaussians):
+        self.device, self.stream = device, _stream(device)
+        self.s, self._keep_s = _settings(*settings, device, self.stream)
+        self.g, self.keep_g, _ = _gaussians(*gaussians, device)
+
+    def call(self, what, fn, *middle, release=False):
+        """(return value, {kind: buffer}); release: the buffers are scratch, handed back to torch's allocator."""
+        _begin(self.device)
+        rc = fn(ctypes.byref(self.s), ctypes.byref(self.g), *middle, _ALLOC_CB, None, self.stream)
+        _check(rc, what)
+        bufs = _tls.buffers
+        if release:
+            _tls.buffers = {}
+        return int(rc), bufs
 
 
 # ---------------------------------------------------------------------------------------------
@@ -327,8 +407,7 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
             REUSE_STATS["misses"] += 1
         _begin(device)
         if capacity > 0:
-            if status is None or status.device != device or status.numel() < 4:
-                raise RuntimeError("static forward needs a device status tensor of 4 int32")
+            _check_status(status, device)
             n = lib.gsr_forward_static(ctypes.byref(s), ctypes.byref(g), int(capacity), status.data_ptr(),
                                        out_color.data_ptr(), out_depth.data_ptr(), radii.data_ptr(), _ALLOC_CB, None,
                                        stream)
@@ -404,9 +483,10 @@ def rasterize_gaussians_dual(background, means3D, colors, colors2, opacity, scal
     gsr_forward_dual_static (no host synchronisation; `status` is a device int32[4]
     receiving the counters, and num_rendered is the capacity).  alive (static mode only): a
     device uint8 [P] mask, 0 = pruned (gsr_forward_dual_static_alive: culled, radius 0).
-    xform (static mode only): (means_world, unnorm_rot, logit_opac, log_scales, scale_cols, cam_q ptr, cam_t ptr,
-    q_stride, w2c) -- the mapping transform inside preprocess (gsr_forward_dual_static_xf): means3D, rotations,
-    colors2, opacity and scales are then its outputs."""
+    xform (static mode only): a TrackXform -- the mapping transform inside preprocess
+    (gsr_forward_dual_static_xf: it always stores the rendervars and its mask is the `alive` argument; the record's
+    store_rendervars and alive fields are the tracking forward's and are not read here).
+    The library's arguments by segment: colors2 [, xform] [, capacity, status], the four outputs [, alive]."""
     device = means3D.device
     if device.type != "cuda":
         raise RuntimeError("splatam_amd rasterizer runs on ROCm devices only (no CPU fallback); "
@@ -416,56 +496,33 @@ def rasterize_gaussians_dual(background, means3D, colors, colors2, opacity, scal
     f32 = dict(dtype=torch.float32, device=device)
     if colors2 is None or colors2.shape != (P, 3):
         raise RuntimeError("colors2 must have dimensions (num_points, 3)")
+    if capacity <= 0 and (alive is not None or xform is not None):
+        raise RuntimeError("the alive mask and the fused transform need the static (capacity > 0) forward")
     with torch.cuda.device(device):
-        s, keep_s = _settings(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier,
-                              degree, prefiltered, device)
-        g, keep_g, _ = _gaussians(means3D, sh, colors, opacity, scales, rotations, cov3D_precomp, device)
+        fr = _Frame(device, (background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier,
+                             degree, prefiltered), (means3D, sh, colors, opacity, scales, rotations, cov3D_precomp))
         c2 = _dev_f32(colors2, device, "colors2")
         out_color = torch.empty(3, H, W, **f32)
         out_color2 = torch.empty(3, H, W, **f32)
         out_depth = torch.empty(1, H, W, **f32)
         radii = torch.empty(P, dtype=torch.int32, device=device)
-        _begin(device)
+        fn, static, mask = lib.gsr_forward_dual, (), ()
         if capacity > 0:
-            if status is None or status.device != device or status.numel() < 4:
-                raise RuntimeError("static dual forward needs a device status tensor of 4 int32")
-            if alive is not None:
-                if alive.device != device or alive.dtype != torch.uint8 or alive.numel() != P or \
-                        not alive.is_contiguous():
-                    raise RuntimeError("alive must be a contiguous uint8 tensor of P entries on the render device")
+            _check_status(status, device)
+            _check_alive(alive, P, device)
+            static = (int(capacity), status.data_ptr())
             if xform is not None:
-                outs = (means3D, colors2, opacity, scales, rotations)
-                if any(not t.is_contiguous() or t.dtype != torch.float32 or t.device != device for t in outs):
-                    raise RuntimeError("forward_dual_static_xf: the rendervar outputs must be contiguous float32 "
-                                       "tensors on the device")
-                mw, ur, lo, ls, scols, q_ptr, t_ptr, qs, w2c = xform[:9]
-                xf = GsrTrackXform(means_world=mw.data_ptr(), unnorm_rot=ur.data_ptr(), logit_opac=lo.data_ptr(),
-                                   log_scales=ls.data_ptr(), scale_cols=int(scols), cam_q=q_ptr, cam_t=t_ptr,
-                                   q_stride=int(qs), w2c=w2c.data_ptr(), store_rendervars=1, alive=_ptr(alive))
-                n = lib.gsr_forward_dual_static_xf(ctypes.byref(s), ctypes.byref(g), _ptr(c2), ctypes.byref(xf),
-                                                   int(capacity), status.data_ptr(), out_color.data_ptr(),
-                                                   out_color2.data_ptr(), out_depth.data_ptr(),
-                                                   radii.data_ptr() if P else None, _ALLOC_CB, None, _stream(device))
+                _check_xform_outputs(device, means3D, colors2, opacity, scales, rotations)
+                xf = xform_struct(xform)
+                xf.store_rendervars, xf.alive = 1, _ptr(alive)  # (as before the record: its own two are not read)
+                fn, static = lib.gsr_forward_dual_static_xf, (ctypes.byref(xf),) + static
             elif alive is not None:
-                n = lib.gsr_forward_dual_static_alive(ctypes.byref(s), ctypes.byref(g), _ptr(c2), int(capacity),
-                                                      status.data_ptr(), out_color.data_ptr(), out_color2.data_ptr(),
-                                                      out_depth.data_ptr(), radii.data_ptr() if P else None,
-                                                      alive.data_ptr() if P else None, _ALLOC_CB, None,
-                                                      _stream(device))
+                fn, mask = lib.gsr_forward_dual_static_alive, (alive.data_ptr() if P else None,)
             else:
-                n = lib.gsr_forward_dual_static(ctypes.byref(s), ctypes.byref(g), _ptr(c2), int(capacity),
-                                                status.data_ptr(), out_color.data_ptr(), out_color2.data_ptr(),
-                                                out_depth.data_ptr(), radii.data_ptr() if P else None, _ALLOC_CB,
-                                                None, _stream(device))
-        else:
-            if alive is not None or xform is not None:
-                raise RuntimeError("the alive mask and the fused transform need the static (capacity > 0) forward")
-            n = lib.gsr_forward_dual(ctypes.byref(s), ctypes.byref(g), _ptr(c2), out_color.data_ptr(),
-                                     out_color2.data_ptr(), out_depth.data_ptr(), radii.data_ptr() if P else None,
-                                     _ALLOC_CB, None, _stream(device))
-        _check(n, "rasterize_gaussians_dual")
-        bufs = _tls.buffers
-        return (int(n), out_color, out_color2, radii, bufs[0], bufs[1], bufs[2], out_depth)
+                fn = lib.gsr_forward_dual_static
+        n, bufs = fr.call("rasterize_gaussians_dual", fn, _ptr(c2), *static, out_color.data_ptr(),
+                          out_color2.data_ptr(), out_depth.data_ptr(), radii.data_ptr() if P else None, *mask)
+        return (n, out_color, out_color2, radii, bufs[0], bufs[1], bufs[2], out_depth)
 
 
 def rasterize_gaussians_dual_backward(background, means3D, radii, colors, colors2, scales, rotations, scale_modifier,
@@ -495,32 +552,22 @@ def rasterize_gaussians_dual_backward(background, means3D, radii, colors, colors
     if P == 0:
         return (out[0], out[1], dcolors2, *out[2:])
     with torch.cuda.device(device):
-        s, keep_s = _settings(background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier,
-                              degree, False, device)
-        g, keep_g, _ = _gaussians(means3D, sh, colors, None, scales, rotations, cov3D_precomp, device)
+        # opacities are not an input of the backward (rasterize_points.cu:117-139): they live in geomBuffer
+        fr = _Frame(device, (background, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, H, W, scale_modifier,
+                             degree, False), (means3D, sh, colors, None, scales, rotations, cov3D_precomp))
         c2 = _dev_f32(colors2, device, "colors2")
         dpix = _dev_f32(dL_dout_color, device, "dL_dout_color")
         dpix2 = _dev_f32(dL_dout_color2, device, "dL_dout_color2")
         radii_c = radii.to(device=device, dtype=torch.int32).contiguous()
         grads = GsrGrads(*[o.data_ptr() if (o is not None and o.numel() > 0) else None for o in out])
-        _begin(device)
+        fn, step = lib.gsr_backward_dual, ()
         if sh_adam is not None:
-            if keep_g[1] is None or keep_g[1].data_ptr() != sh.data_ptr():
+            if fr.keep_g[1] is None or fr.keep_g[1].data_ptr() != sh.data_ptr():
                 raise RuntimeError("sh_adam steps the SH coefficients in place: sh must be contiguous float32")
-            rc = lib.gsr_backward_dual_sh_adam(
-                ctypes.byref(s), ctypes.byref(g), radii_c.data_ptr(), _ptr(c2), dpix.data_ptr(), dpix2.data_ptr(),
-                int(R), geomBuffer.data_ptr(), binningBuffer.data_ptr() if binningBuffer.numel() else None,
-                imageBuffer.data_ptr(), ctypes.byref(grads), dcolors2.data_ptr() if dcolors2 is not None else None,
-                int(dl2_channels), ctypes.byref(sh_adam), _ALLOC_CB, None, _stream(device))
-        else:
-            rc = lib.gsr_backward_dual(ctypes.byref(s), ctypes.byref(g), radii_c.data_ptr(), _ptr(c2),
-                                       dpix.data_ptr(), dpix2.data_ptr(), int(R), geomBuffer.data_ptr(),
-                                       binningBuffer.data_ptr() if binningBuffer.numel() else None,
-                                       imageBuffer.data_ptr(), ctypes.byref(grads),
-                                       dcolors2.data_ptr() if dcolors2 is not None else None, int(dl2_channels),
-                                       _ALLOC_CB, None, _stream(device))
-        _check(rc, "rasterize_gaussians_dual_backward")
-        _tls.buffers = {}
+            fn, step = lib.gsr_backward_dual_sh_adam, (ctypes.byref(sh_adam),)
+        fr.call("rasterize_gaussians_dual_backward", fn, radii_c.data_ptr(), _ptr(c2), dpix.data_ptr(),
+                dpix2.data_ptr(), *_forward_state(R, geomBuffer, binningBuffer, imageBuffer), ctypes.byref(grads),
+                _ptr(dcolors2), int(dl2_channels), *step, release=True)
         return (out[0], out[1], dcolors2, *out[2:])
 
 
@@ -579,43 +626,25 @@ def track_backward_dual(settings, means3D, radii, colors, colors2, scales, rotat
     a fused forward (track_forward_dual_static(records=...)): gsr_track_backward_dual_records, only the
     per-Gaussian backward runs and the gradient images are not read (may be None)."""
     device = means3D.device
-    H, W = int(settings.image_height), int(settings.image_width)
     with torch.cuda.device(device):
-        st = settings
-        s, keep_s = _settings(st.bg, st.viewmatrix, st.projmatrix, st.campos, st.tanfovx, st.tanfovy, H, W,
-                              st.scale_modifier, st.sh_degree, False, device)
-        g, keep_g, _ = _gaussians(means3D, None, colors, None, scales, rotations, None, device)
+        fr = _Frame(device, _settings_of(settings, False), (means3D, None, colors, None, scales, rotations, None))
         c2 = _dev_f32(colors2, device, "colors2")
-        dpix = _dev_f32(dL_dout_color, device, "dL_dout_color")
-        dpix2 = _dev_f32(dL_dout_color2, device, "dL_dout_color2")
-        lr_q = lr_t = b1 = b2 = eps = 0.0
-        state = None
-        if adam is not None:
-            lr_q, lr_t, b1, b2, eps, state = adam
-        _begin(device)
+        lr_q, lr_t, b1, b2, eps, state = adam if adam is not None else (0.0, 0.0, 0.0, 0.0, 0.0, None)
+        # the library's arguments by segment: radii, colors2 [, the gradient images], the forward's state, the pose
+        # chain (the map, the pose column, the Adam step or the gradient's address, ...) [, records]
+        fn, what, images, rec = lib.gsr_track_backward_dual, "track_backward_dual", (), ()
         if records is not None:
-            rc = lib.gsr_track_backward_dual_records(
-                ctypes.byref(s), ctypes.byref(g), radii.data_ptr(), _ptr(c2), int(R), geomBuffer.data_ptr(),
-                binningBuffer.data_ptr() if binningBuffer.numel() else None, imageBuffer.data_ptr(),
-                means_world.data_ptr(), unnorm_rot.data_ptr(), int(scale_cols), cam_q_ptr, cam_t_ptr, int(q_stride),
-                w2c.data_ptr(), float(lr_q), float(lr_t), float(b1), float(b2), float(eps),
-                state.data_ptr() if state is not None else None, dq_ptr, dt_ptr, scratch.data_ptr(),
-                ctypes.byref(track) if track is not None else None,
-                log_scales.data_ptr() if log_scales is not None else None, records.data_ptr(), _ALLOC_CB, None,
-                _stream(device))
-            _check(rc, "track_backward_dual_records")
-            _tls.buffers = {}
-            return
-        rc = lib.gsr_track_backward_dual(
-            ctypes.byref(s), ctypes.byref(g), radii.data_ptr(), _ptr(c2), dpix.data_ptr(), dpix2.data_ptr(), int(R),
-            geomBuffer.data_ptr(), binningBuffer.data_ptr() if binningBuffer.numel() else None,
-            imageBuffer.data_ptr(), means_world.data_ptr(), unnorm_rot.data_ptr(), int(scale_cols),
-            cam_q_ptr, cam_t_ptr, int(q_stride), w2c.data_ptr(), float(lr_q), float(lr_t), float(b1), float(b2),
-            float(eps), state.data_ptr() if state is not None else None, dq_ptr, dt_ptr, scratch.data_ptr(),
-            ctypes.byref(track) if track is not None else None,
-            log_scales.data_ptr() if log_scales is not None else None, _ALLOC_CB, None, _stream(device))
-        _check(rc, "track_backward_dual")
-        _tls.buffers = {}
+            fn, what, rec = lib.gsr_track_backward_dual_records, "track_backward_dual_records", (records.data_ptr(),)
+        else:
+            dpix = _dev_f32(dL_dout_color, device, "dL_dout_color")  # (named: alive until the call returns)
+            dpix2 = _dev_f32(dL_dout_color2, device, "dL_dout_color2")
+            images = (dpix.data_ptr(), dpix2.data_ptr())
+        fr.call(what, fn, radii.data_ptr(), _ptr(c2), *images,
+                *_forward_state(R, geomBuffer, binningBuffer, imageBuffer), means_world.data_ptr(),
+                unnorm_rot.data_ptr(), int(scale_cols), cam_q_ptr, cam_t_ptr, int(q_stride), w2c.data_ptr(),
+                float(lr_q), float(lr_t), float(b1), float(b2), float(eps), _ptr(state), dq_ptr, dt_ptr,
+                scratch.data_ptr(), ctypes.byref(track) if track is not None else None, _ptr(log_scales), *rec,
+                release=True)
 
 
 def terms_ptr(terms: torch.Tensor, device) -> int:
@@ -632,10 +661,8 @@ def track_forward_dual_static(settings, means3D, colors, colors2, opacity, scale
     """gsr_track_forward_dual_static (include/gsr_glue.h): the static dual forward with SplaTAM's
     tracking L1 loss and its gradient images formed in the render epilogue.  Returns (num_rendered=capacity,
     color, color2, radii, geomBuffer, binningBuffer, imgBuffer, depth, loss, dL_dim, dL_ddepth_sil).
-    xform = (means_world, unnorm_rot, logit_opac, log_scales, scale_cols, cam_q_ptr, cam_t_ptr, q_stride, w2c,
-    store[, alive]): gsr_track_forward_dual_static_xf -- the tracking transform runs inside preprocess and means3D,
-    colors2, opacity, scales and rotations are its OUTPUTS (preallocated contiguous float32; written only
-    when store is true).  records (with xform; device float32 of lib.gsr_track_records_floats(capacity)):
+    xform (a TrackXform): gsr_track_forward_dual_static_xf -- the tracking transform runs inside preprocess.
+    records (with xform; device float32 of lib.gsr_track_records_floats(capacity)):
     gsr_track_forward_backward_dual_static_xf -- the tracking render backward runs in the same launch
     and leaves its per-instance sums in records (track_backward_dual(records=...)); dL_dim / dL_ddepth_sil
     come back None (not formed).  images=False (with records): the rendered images are not stored either
@@ -647,71 +674,46 @@ def track_forward_dual_static(settings, means3D, colors, colors2, opacity, scale
     P = means3D.size(0)
     H, W = int(st.image_height), int(st.image_width)
     f32 = dict(dtype=torch.float32, device=device)
+    if records is not None and xform is None:
+        raise RuntimeError("track_forward_dual_static: records needs the transform-fused forward (xform)")
+    if not images and records is None:
+        raise RuntimeError("track_forward_dual_static: images=False needs the fused render (xform and records)")
     with torch.cuda.device(device):
-        s, keep_s = _settings(st.bg, st.viewmatrix, st.projmatrix, st.campos, st.tanfovx, st.tanfovy, H, W,
-                              st.scale_modifier, st.sh_degree, st.prefiltered, device)
-        g, keep_g, _ = _gaussians(means3D, None, colors, opacity, scales, rotations, None, device)
+        fr = _Frame(device, _settings_of(st, st.prefiltered), (means3D, None, colors, opacity, scales, rotations, None))
         c2 = _dev_f32(colors2, device, "colors2")
         gi, gd, sd = (_dev_f32(gt_im, device, "gt_im"), _dev_f32(gt_depth, device, "gt_depth"),
                       _dev_f32(seed, device, "seed"))
-        if not images and (xform is None or records is None):
-            raise RuntimeError("track_forward_dual_static: images=False needs the fused render (xform and records)")
         out_color = out_color2 = out_depth = None
         if images:
             out_color, out_color2 = torch.empty(3, H, W, **f32), torch.empty(3, H, W, **f32)
             out_depth = torch.empty(1, H, W, **f32)
         radii = torch.empty(P, dtype=torch.int32, device=device)
         loss = torch.empty((), **f32)
-        dim = dds = None
-        if records is None:
+        _check_status(status, device)
+        # The library's arguments by segment: colors2 [, xform], capacity, status, the image outputs and radii | the
+        # L1 block (targets, threshold, weights, seed, loss) [, terms] | the gradient images or, with the render
+        # backward in the same launch, its records -- scratch between them.  The entry point's name says which
+        # segments it takes.
+        name, xf, dim, dds = "gsr_track_forward_dual_static", (), None, None
+        if xform is not None:
+            _check_xform_outputs(device, means3D, colors2, opacity, scales, rotations)
+            _check_alive(xform.alive, P, device)
+            xf_struct = xform_struct(xform)
+            name, xf = name + "_xf", (ctypes.byref(xf_struct),)
+        if records is not None:
+            if (records.device != device or records.dtype != torch.float32 or not records.is_contiguous() or
+                    records.numel() < lib.gsr_track_records_floats(int(capacity))):
+                raise RuntimeError("records: contiguous float32 of gsr_track_records_floats(capacity) on the device")
+            name = "gsr_track_forward_backward_dual_static_xf"
+            tail = (scratch.data_ptr(), records.data_ptr())
+        else:
             dim, dds = torch.empty(3, H, W, **f32), torch.empty(3, H, W, **f32)
-        if status is None or status.device != device or status.numel() < 4:
-            raise RuntimeError("static dual forward needs a device status tensor of 4 int32")
+            tail = (dim.data_ptr(), dds.data_ptr(), scratch.data_ptr())
         # the _terms sibling of each call: `terms` behind `loss`
         tp = () if terms is None else (terms_ptr(terms, device),)
-        _begin(device)
-        if xform is not None:
-            outs = (means3D, colors2, opacity, scales, rotations)
-            if any(t is None or not t.is_contiguous() or t.dtype != torch.float32 or t.device != device for t in outs):
-                raise RuntimeError("track_forward_dual_static_xf: the rendervar outputs must be contiguous float32 "
-                                   "tensors on the device")
-            mw, ur, lo, ls, scols, q_ptr, t_ptr, qs, w2c, store = xform[:10]
-            alive = xform[10] if len(xform) > 10 else None
-            if alive is not None and (alive.dtype != torch.uint8 or alive.numel() != P or alive.device != device
-                                      or not alive.is_contiguous()):
-                raise RuntimeError("alive: contiguous uint8 of P entries on the device")
-            xf = GsrTrackXform(means_world=mw.data_ptr(), unnorm_rot=ur.data_ptr(), logit_opac=lo.data_ptr(),
-                               log_scales=ls.data_ptr(), scale_cols=int(scols), cam_q=q_ptr, cam_t=t_ptr,
-                               q_stride=int(qs), w2c=w2c.data_ptr(), store_rendervars=int(bool(store)),
-                               alive=_ptr(alive))
-            if records is not None:
-                if (records.device != device or records.dtype != torch.float32 or not records.is_contiguous() or
-                        records.numel() < lib.gsr_track_records_floats(int(capacity))):
-                    raise RuntimeError("records: contiguous float32 of gsr_track_records_floats(capacity) on the device")
-                fn = lib.gsr_track_forward_backward_dual_static_xf_terms if tp else \
-                    lib.gsr_track_forward_backward_dual_static_xf
-                n = fn(
-                    ctypes.byref(s), ctypes.byref(g), _ptr(c2), ctypes.byref(xf), int(capacity), status.data_ptr(),
-                    _ptr(out_color), _ptr(out_color2), _ptr(out_depth), radii.data_ptr() if P else None,
-                    gi.data_ptr(), gd.data_ptr(), float(sil_thres), float(w_im), float(w_depth), sd.data_ptr(),
-                    loss.data_ptr(), *tp, scratch.data_ptr(), records.data_ptr(), _ALLOC_CB, None, _stream(device))
-                _check(n, "track_forward_backward_dual_static_xf")
-                bufs = _tls.buffers
-                return (int(n), out_color, out_color2, radii, bufs[0], bufs[1], bufs[2], out_depth, loss, None, None)
-            n = (lib.gsr_track_forward_dual_static_xf_terms if tp else lib.gsr_track_forward_dual_static_xf)(
-                ctypes.byref(s), ctypes.byref(g), _ptr(c2), ctypes.byref(xf), int(capacity), status.data_ptr(),
-                out_color.data_ptr(), out_color2.data_ptr(), out_depth.data_ptr(), radii.data_ptr() if P else None,
-                gi.data_ptr(), gd.data_ptr(), float(sil_thres), float(w_im), float(w_depth), sd.data_ptr(),
-                loss.data_ptr(), *tp, dim.data_ptr(), dds.data_ptr(), scratch.data_ptr(), _ALLOC_CB, None,
-                _stream(device))
-            _check(n, "track_forward_dual_static_xf")
-            bufs = _tls.buffers
-            return (int(n), out_color, out_color2, radii, bufs[0], bufs[1], bufs[2], out_depth, loss, dim, dds)
-        n = (lib.gsr_track_forward_dual_static_terms if tp else lib.gsr_track_forward_dual_static)(
-            ctypes.byref(s), ctypes.byref(g), _ptr(c2), int(capacity), status.data_ptr(), out_color.data_ptr(),
-            out_color2.data_ptr(), out_depth.data_ptr(), radii.data_ptr() if P else None, gi.data_ptr(),
-            gd.data_ptr(), float(sil_thres), float(w_im), float(w_depth), sd.data_ptr(), loss.data_ptr(), *tp,
-            dim.data_ptr(), dds.data_ptr(), scratch.data_ptr(), _ALLOC_CB, None, _stream(device))
-        _check(n, "track_forward_dual_static")
-        bufs = _tls.buffers
-        return (int(n), out_color, out_color2, radii, bufs[0], bufs[1], bufs[2], out_depth, loss, dim, dds)
+        n, bufs = fr.call(name[4:], getattr(lib, name + "_terms" if tp else name), _ptr(c2), *xf, int(capacity),
+                          status.data_ptr(), _ptr(out_color), _ptr(out_color2), _ptr(out_depth),
+                          radii.data_ptr() if P else None, gi.data_ptr(), gd.data_ptr(), float(sil_thres),
+                          float(w_im), float(w_depth), sd.data_ptr(), loss.data_ptr(), *tp, *tail)
+        return (n, out_color, out_color2, radii, bufs[0], bufs[1], bufs[2], out_depth, loss, dim, dds)
+

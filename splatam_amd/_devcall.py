@@ -28,6 +28,25 @@ def check_rc(rc: int, what: str):
         raise RuntimeError(f"{what}: {lib.gsr_last_error().decode(errors='replace')}")
 
 
+TILE_SORT_CAP = 4096  # longest tile list the static mode handles (render_fwd's per-tile sort)
+
+
+def capacity_from_probes(probes, headroom: float, min_extra: int) -> int:
+    """The static binning capacity for frames that probed as `probes` ((num_rendered, longest tile list) each):
+    headroom times the largest num_rendered plus min_extra.  A tile list over TILE_SORT_CAP is refused."""
+    longest = max(p[1] for p in probes)
+    if longest > TILE_SORT_CAP:
+        raise RuntimeError(f"a tile list of {longest} > {TILE_SORT_CAP}: use the eager (synchronous) path")
+    return max(1, int(headroom * max(p[0] for p in probes)) + int(min_extra))
+
+
+def status_overflowed(status: torch.Tensor, capacity: int) -> bool:
+    """True if any row of a static-mode status tensor [iters, 4] (sticky across replays, include/gsr.h) shows more
+    instances than `capacity`, a tile list over TILE_SORT_CAP or a prefiltered violation.  One host sync."""
+    st = status.cpu()
+    return bool((st[:, 0] > capacity).any() or (st[:, 2] > TILE_SORT_CAP).any() or (st[:, 1] != 0).any())
+
+
 def f32(v, device) -> torch.Tensor:
     """v as a float32 scalar tensor (an elementwise op with it rounds like the kernels' float)."""
     return torch.tensor(float(v), dtype=torch.float32, device=device)

@@ -20,6 +20,7 @@ import os
 
 import torch
 
+from ._devcall import check_rc
 from ._lib import lib
 
 # tracking transform fused into the rasterizer's preprocess in the static tracking iteration
@@ -34,13 +35,18 @@ _RENDER_FUSED = (os.environ.get("GSR_TRACK_RENDER_FUSED", "1") != "0" and
 _XF_STORE = False
 
 
-def _check(rc: int, what: str):
-    if rc < 0:
-        raise RuntimeError(f"{what}: {lib.gsr_last_error().decode(errors='replace')}")
-
-
 def _stream(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _col(x: torch.Tensor, t: int) -> int:
+    """The address of column t of a contiguous float32 (1, 3 or 4, T) pose tensor (its rows are T floats apart)."""
+    return x.data_ptr() + 4 * t
+
+
+def _pose_cols(cam_rots, cam_trans, t):
+    """(cam_q, cam_t): frame t's quaternion and translation columns, as the library takes them with q_stride = T."""
+    return _col(cam_rots, t), _col(cam_trans, t)
 
 
 def _byref(s):
@@ -108,6 +114,23 @@ def _scratch(t: torch.Tensor, n: int) -> torch.Tensor:
     return buf
 
 
+def _rendervars(means_world):
+    """The transform's five outputs, unwritten: (means_cam, rotations, depth_colors, opacities, scales)."""
+    P, f32 = means_world.shape[0], dict(dtype=torch.float32, device=means_world.device)
+    return (torch.empty(P, 3, **f32), torch.empty(P, 4, **f32), torch.empty(P, 3, **f32), torch.empty(P, 1, **f32),
+            torch.empty(P, 3, **f32))
+
+
+def _transform_fwd(what, means_world, unnorm_rot, logit_opac, log_scales, cam_rots, cam_trans, t, w2c, outs):
+    """gsr_track_transform_fwd: the world-frame map (contiguous float32) through frame t's pose and w2c into
+    `outs` (_rendervars); the tracking and the mapping transform are the same launch."""
+    rc = lib.gsr_track_transform_fwd(means_world.shape[0], means_world.data_ptr(), unnorm_rot.data_ptr(),
+                                     logit_opac.data_ptr(), log_scales.data_ptr(), log_scales.shape[1],
+                                     *_pose_cols(cam_rots, cam_trans, t), cam_rots.shape[-1], w2c.data_ptr(),
+                                     *[o.data_ptr() for o in outs], _stream(means_world))
+    check_rc(rc, what)
+
+
 class _TrackTransform(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cam_rots, cam_trans, means_world, unnorm_rot, logit_opac, log_scales, w2c, time_idx,
@@ -120,21 +143,10 @@ class _TrackTransform(torch.autograd.Function):
         if cam_rots.shape != (1, 4, T) or cam_trans.shape != (1, 3, T):
             raise RuntimeError("cam_unnorm_rots / cam_trans must be (1,4,T) / (1,3,T)")
         t = int(time_idx)
-        P = means_world.shape[0]
         scols = log_scales.shape[1]
-        dev = means_world.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        means_cam = torch.empty(P, 3, **f32)
-        rot = torch.empty(P, 4, **f32)
-        dcol = torch.empty(P, 3, **f32)
-        opac = torch.empty(P, 1, **f32)
-        scales = torch.empty(P, 3, **f32)
-        rc = lib.gsr_track_transform_fwd(P, means_world.data_ptr(), unnorm_rot.data_ptr(), logit_opac.data_ptr(),
-                                         log_scales.data_ptr(), scols, cam_rots.data_ptr() + 4 * t,
-                                         cam_trans.data_ptr() + 4 * t, T, w2c.data_ptr(), means_cam.data_ptr(),
-                                         rot.data_ptr(), dcol.data_ptr(), opac.data_ptr(), scales.data_ptr(),
-                                         _stream(means_world))
-        _check(rc, "track_transform_fwd")
+        means_cam, rot, dcol, opac, scales = outs = _rendervars(means_world)
+        _transform_fwd("track_transform_fwd", means_world, unnorm_rot, logit_opac, log_scales, cam_rots, cam_trans,
+                       t, w2c, outs)
         ctx.set_materialize_grads(False)  # no zero-filled grads for unused outputs
         # one call: a second mark_non_differentiable replaces the first set
         if scols == 1:  # isotropic maps: rotations do not depend on the pose either
@@ -163,23 +175,23 @@ class _TrackTransform(torch.autograd.Function):
         if opt is not None:  # optimizer step fused into the backward: the pose is updated in place
             scratch = _scratch(means_world, lib.gsr_track_scratch_floats(P))
             rc = lib.gsr_track_transform_bwd_adam(
-                P, means_world.data_ptr(), unnorm_rot.data_ptr(), scols, cam_rots.data_ptr() + 4 * t,
-                cam_trans.data_ptr() + 4 * t, T, means_cam.data_ptr(), w2c.data_ptr(), g_means.data_ptr(),
+                P, means_world.data_ptr(), unnorm_rot.data_ptr(), scols, *_pose_cols(cam_rots, cam_trans, t), T,
+                means_cam.data_ptr(), w2c.data_ptr(), g_means.data_ptr(),
                 g_rot.data_ptr() if g_rot is not None else None, g_dcol.data_ptr() if g_dcol is not None else None,
                 opt.lr_q, opt.lr_t, float(opt.betas[0]), float(opt.betas[1]), opt.eps, opt.state.data_ptr(),
                 scratch.data_ptr(), _byref(opt.track()), _stream(means_world))
-            _check(rc, "track_transform_bwd_adam")
+            check_rc(rc, "track_transform_bwd_adam")
             return none
         dq = torch.zeros_like(cam_rots)
         dt = torch.zeros_like(cam_trans)
         scratch = _scratch(means_world, lib.gsr_track_scratch_floats(P))
         rc = lib.gsr_track_transform_bwd(P, means_world.data_ptr(), unnorm_rot.data_ptr(), scols,
-                                         cam_rots.data_ptr() + 4 * t, means_cam.data_ptr(), w2c.data_ptr(),
+                                         _col(cam_rots, t), means_cam.data_ptr(), w2c.data_ptr(),
                                          g_means.data_ptr(), g_rot.data_ptr() if g_rot is not None else None,
                                          g_dcol.data_ptr() if g_dcol is not None else None,
-                                         dq.data_ptr() + 4 * t, dt.data_ptr() + 4 * t, T, scratch.data_ptr(),
+                                         *_pose_cols(dq, dt, t), T, scratch.data_ptr(),
                                          _stream(means_world))
-        _check(rc, "track_transform_bwd")
+        check_rc(rc, "track_transform_bwd")
         return dq, dt, None, None, None, None, None, None, None
 
 
@@ -204,11 +216,22 @@ def _track_l1(H, W, im, ds, gt_im, gt_d, sil_thres, w_im, w_depth, seed, loss, t
         fn = lib.gsr_track_l1_fwd_bwd_terms if tp else lib.gsr_track_l1_fwd_bwd
         rc = fn(*head, seed.data_ptr(), loss.data_ptr(), *tp, dim.data_ptr(), dds.data_ptr(), scratch.data_ptr(),
                 _stream(im))
-        _check(rc, "track_l1_fwd_bwd")
+        check_rc(rc, "track_l1_fwd_bwd")
     else:
         fn = lib.gsr_track_l1_fwd_terms if tp else lib.gsr_track_l1_fwd
         rc = fn(*head, loss.data_ptr(), *tp, scratch.data_ptr(), _stream(im))
-        _check(rc, "track_l1_fwd")
+        check_rc(rc, "track_l1_fwd")
+
+
+def _l1_bwd(im, ds, gt_im, gt_d, sil_thres, w_im, w_depth, g):
+    """gsr_track_l1_bwd: the tracking L1 loss's gradient images (dL/dim, dL/ddepth_sil) for the loss gradient g."""
+    _, H, W = im.shape
+    g = g.contiguous()
+    dim, dds = torch.empty_like(im), torch.empty_like(ds)
+    rc = lib.gsr_track_l1_bwd(H, W, im.data_ptr(), ds.data_ptr(), gt_im.data_ptr(), gt_d.data_ptr(), float(sil_thres),
+                              float(w_im), float(w_depth), g.data_ptr(), dim.data_ptr(), dds.data_ptr(), _stream(im))
+    check_rc(rc, "track_l1_bwd")
+    return dim, dds
 
 
 class _TrackingL1(torch.autograd.Function):
@@ -237,14 +260,7 @@ class _TrackingL1(torch.autograd.Function):
         if ctx.pre is not None and g.data_ptr() == ctx.pre[2].data_ptr():  # seeded with the forward's seed
             return ctx.pre[0], ctx.pre[1], None, None, None, None, None, None, None
         im, depth_sil, gt_im, gt_depth = ctx.saved_tensors
-        sil_thres, w_im, w_depth = ctx.meta
-        _, H, W = im.shape
-        g = g.contiguous()
-        dim = torch.empty_like(im)
-        dds = torch.empty_like(depth_sil)
-        rc = lib.gsr_track_l1_bwd(H, W, im.data_ptr(), depth_sil.data_ptr(), gt_im.data_ptr(), gt_depth.data_ptr(),
-                                  sil_thres, w_im, w_depth, g.data_ptr(), dim.data_ptr(), dds.data_ptr(), _stream(im))
-        _check(rc, "track_l1_bwd")
+        dim, dds = _l1_bwd(im, depth_sil, gt_im, gt_depth, *ctx.meta, g)
         return dim, dds, None, None, None, None, None, None, None
 
 
@@ -331,19 +347,14 @@ class _MapTransform(torch.autograd.Function):
         scols = log_scales.shape[1]
         if colors.shape[0] != P:
             raise RuntimeError("colour parameters must have one row per Gaussian")
-        f32 = dict(dtype=torch.float32, device=means_world.device)
-        means_cam, rot, dcol = torch.empty(P, 3, **f32), torch.empty(P, 4, **f32), torch.empty(P, 3, **f32)
-        opac, scales = torch.empty(P, 1, **f32), torch.empty(P, 3, **f32)
+        means_cam, rot, dcol, opac, scales = outs = _rendervars(means_world)
         if defer is None:
-            rc = lib.gsr_track_transform_fwd(P, means_world.data_ptr(), unnorm_rot.data_ptr(), logit_opac.data_ptr(),
-                                             log_scales.data_ptr(), scols, cam_rots.data_ptr() + 4 * t,
-                                             cam_trans.data_ptr() + 4 * t, T, w2c.data_ptr(), means_cam.data_ptr(),
-                                             rot.data_ptr(), dcol.data_ptr(), opac.data_ptr(), scales.data_ptr(),
-                                             _stream(means_world))
-            _check(rc, "map_transform_fwd")
+            _transform_fwd("map_transform_fwd", means_world, unnorm_rot, logit_opac, log_scales, cam_rots, cam_trans,
+                           t, w2c, outs)
         else:  # the next forward (rasterize_gaussians_dual(xform=...)) forms and writes the five outputs
-            defer.append((means_world, unnorm_rot, logit_opac, log_scales, scols, cam_rots.data_ptr() + 4 * t,
-                          cam_trans.data_ptr() + 4 * t, T, w2c, (cam_rots, cam_trans)))
+            from ._C import TrackXform
+            defer.append(TrackXform(means_world, unnorm_rot, logit_opac, log_scales, scols,
+                                    *_pose_cols(cam_rots, cam_trans, t), T, w2c, keep=(cam_rots, cam_trans)))
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(means_world, unnorm_rot, logit_opac, log_scales, colors, cam_rots, means_cam, w2c)
         ctx.meta = (t, T, scols)
@@ -367,10 +378,10 @@ class _MapTransform(torch.autograd.Function):
             ccols = colors.numel() // max(P, 1)
             rc = lib.gsr_map_transform_bwd_adam(
                 P, means_world.data_ptr(), unnorm_rot.data_ptr(), logit_opac.data_ptr(), log_scales.data_ptr(), scols,
-                colors.data_ptr(), ccols, cam_rots.data_ptr() + 4 * t, T, means_cam.data_ptr(), w2c.data_ptr(),
+                colors.data_ptr(), ccols, _col(cam_rots, t), T, means_cam.data_ptr(), w2c.data_ptr(),
                 g_means.data_ptr(), p(g_rot), p(g_dcol), p(g_opac), p(g_scales), p(g_col), ctypes.byref(st),
                 _stream(means_world))
-            _check(rc, "map_transform_bwd_adam")
+            check_rc(rc, "map_transform_bwd_adam")
             return (None,) * 11
         need = ctx.needs_input_grad
         dm = torch.empty_like(means_world)
@@ -378,10 +389,10 @@ class _MapTransform(torch.autograd.Function):
         dl = torch.empty_like(logit_opac) if need[2] else None
         ds = torch.empty_like(log_scales) if need[3] else None
         rc = lib.gsr_map_transform_bwd(P, unnorm_rot.data_ptr(), logit_opac.data_ptr(), log_scales.data_ptr(), scols,
-                                       cam_rots.data_ptr() + 4 * t, T, means_cam.data_ptr(), w2c.data_ptr(),
+                                       _col(cam_rots, t), T, means_cam.data_ptr(), w2c.data_ptr(),
                                        g_means.data_ptr(), p(g_rot), p(g_dcol), p(g_opac), p(g_scales), dm.data_ptr(),
                                        p(du), p(dl), p(ds), _stream(means_world))
-        _check(rc, "map_transform_bwd")
+        check_rc(rc, "map_transform_bwd")
         return (dm if need[0] else None), du, dl, ds, (g_col if need[4] else None), None, None, None, None, None, None
 
 
@@ -407,7 +418,7 @@ def map_prune(params: dict, alive: torch.Tensor, opac_thr: float, big_thr: float
     rc = lib.gsr_map_prune(P, lo.data_ptr(), ls.data_ptr(), ls.shape[1], float(opac_thr),
                            float(big_thr) if big_thr is not None else 0.0, 1 if big_thr is not None else 0,
                            alive.data_ptr(), _stream(lo))
-    _check(rc, "map_prune")
+    check_rc(rc, "map_prune")
 
 
 def map_transform(params: dict, time_idx: int, w2c: torch.Tensor, color_key: str = "rgb_colors",
@@ -417,7 +428,7 @@ def map_transform(params: dict, time_idx: int, w2c: torch.Tensor, color_key: str
     Returns (means3D_cam, rotations, depth_colors [z,1,z^2], opacities, scales, colours); differentiable
     w.r.t. the Gaussian parameters.  With `adam` the backward applies the mapping optimizer's step in
     place (no .grad is produced); the parameters must then require grad, or autograd never calls it.
-    defer (a list): no launch -- the transform's inputs are appended to it and the next
+    defer (a list): no launch -- the transform's inputs are appended to it (a _C.TrackXform) and the next
     rasterize_gaussians_dual(xform=defer[0]) forms the five outputs inside its preprocess (static mode,
     precomputed colours); nothing may read them before that forward."""
     if adam is not None and not params["means3D"].requires_grad:
@@ -442,7 +453,7 @@ class _MappingLoss(torch.autograd.Function):
         rc = lib.gsr_map_loss_fwd(H, W, im.data_ptr(), depth_sil.data_ptr(), gt_im.data_ptr(), gt_depth.data_ptr(),
                                   float(w_im), float(w_depth), loss.data_ptr(), state.data_ptr(), scratch.data_ptr(),
                                   _stream(im))
-        _check(rc, "map_loss_fwd")
+        check_rc(rc, "map_loss_fwd")
         ctx.save_for_backward(im, depth_sil, gt_im, gt_depth, state)
         ctx.meta = (float(w_im), float(w_depth))
         return loss
@@ -457,7 +468,7 @@ class _MappingLoss(torch.autograd.Function):
         rc = lib.gsr_map_loss_bwd(H, W, im.data_ptr(), depth_sil.data_ptr(), gt_im.data_ptr(), gt_depth.data_ptr(),
                                   w_im, w_depth, g.data_ptr(), state.data_ptr(), dim.data_ptr(), dds.data_ptr(),
                                   _stream(im))
-        _check(rc, "map_loss_bwd")
+        check_rc(rc, "map_loss_bwd")
         return dim, dds, None, None, None, None
 
 
@@ -507,7 +518,7 @@ class FusedAdam(torch.optim.Optimizer):
                 with torch.cuda.device(dev):
                     rc = lib.gsr_adam_step(len(chunk), arr, step, float(betas[0]), float(betas[1]), float(eps),
                                            torch.cuda.current_stream(dev).cuda_stream)
-                _check(rc, "adam_step")
+                check_rc(rc, "adam_step")
         return loss
 
 
@@ -529,28 +540,33 @@ class _TrackIteration(torch.autograd.Function):
         ls = _f32c(params["log_scales"].detach(), "log_scales")
         w2c = _f32c(curr["w2c"], "w2c")
         T = cam_rots.shape[-1]
-        P, scols = mw.shape[0], ls.shape[1]
-        dev = mw.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        means, rot, dcol = torch.empty(P, 3, **f32), torch.empty(P, 4, **f32), torch.empty(P, 3, **f32)
-        opac, scales = torch.empty(P, 1, **f32), torch.empty(P, 3, **f32)
+        scols = ls.shape[1]
+        f32 = dict(dtype=torch.float32, device=mw.device)
+        means, rot, dcol, opac, scales = _rendervars(mw)
         rgb = _f32c(params["rgb_colors"].detach(), "rgb_colors")
         gt_im, gt_d = _f32c(curr["im"], "gt_im"), _f32c(curr["depth"], "gt_depth")
         H, W = cam.image_height, cam.image_width
-        ctx.pre = None
-        if alive is not None and not (seed is not None and capacity > 0 and _XF_FUSED):
+        static = seed is not None and capacity > 0  # loss + gradient images in the render epilogue
+        fused = static and _XF_FUSED                # ... and the transform inside preprocess
+        if alive is not None and not fused:
             raise RuntimeError("tracking_iteration: an alive mask needs the static, transform-fused form "
                                "(capacity > 0, a static seed)")
-        if seed is not None and capacity > 0 and _XF_FUSED:
-            # static mode, static seed: the transform inside preprocess (gsr_track_forward_dual_static_xf),
-            # loss + gradient images in the render epilogue
+        if seed is not None:
             seed = _f32c(seed, "seed")
+        records = log_scales = None
+        # each form gives (n, im, ds, radii, geom, binning, img, loss, dim, dds, records, log_scales)
+        if not fused:
+            _transform_fwd("track_transform_fwd", mw, ur, lo, ls, cam_rots, cam_trans, t, w2c,
+                           (means, rot, dcol, opac, scales))
+        if static:
             scratch = _scratch(mw, lib.gsr_track_forward_scratch_floats(W, H))
-            xform = (mw, ur, lo, ls, scols, cam_rots.data_ptr() + 4 * t, cam_trans.data_ptr() + 4 * t, T, w2c,
-                     _XF_STORE, alive)
-            records = None
-            if _RENDER_FUSED:  # (a static seed promises the backward): the render backward in the forward's launch
-                records = torch.empty(lib.gsr_track_records_floats(capacity), **f32)
+            xform = None
+            if fused:
+                xform = _C.TrackXform(mw, ur, lo, ls, scols, *_pose_cols(cam_rots, cam_trans, t), T, w2c,
+                                      store_rendervars=_XF_STORE, alive=alive, keep=(cam_rots, cam_trans))
+                if _RENDER_FUSED:  # (a static seed promises the backward): the render backward in the forward's launch
+                    records = torch.empty(lib.gsr_track_records_floats(capacity), **f32)
+                log_scales = None if _XF_STORE else ls  # rendervars not stored: the backward recomputes them
             # images=False (fused render only): the rendered images stay in registers -- the loss and the
             # render backward are in the same launch; nothing reads them afterwards unless the backward is
             # taken from another seed, which then raises
@@ -558,58 +574,27 @@ class _TrackIteration(torch.autograd.Function):
                 cam, means, rgb, dcol, opac, scales, rot, capacity, status, gt_im, gt_d, cfg.sil_thres, cfg.w_im,
                 cfg.w_depth, seed, scratch, xform=xform, records=records, images=images or records is None,
                 terms=terms)
-            ctx.pre = (dim, dds, seed)
-            ctx.records = records
-            ctx.save_for_backward(cam_rots, cam_trans, mw, ur, means, rot, dcol, scales, rgb, radii, geom, binning,
-                                  img, im, ds, gt_im, gt_d, w2c)
-            ctx.meta = (t, T, scols, int(n), cam, cfg)
-            ctx.pose_adam = pose_adam
-            ctx.loss_ptr = loss.data_ptr()
-            ctx.log_scales = None if _XF_STORE else ls  # rendervars not stored: the backward recomputes them
-            ctx.mark_non_differentiable(radii)
-            ctx.set_materialize_grads(False)
-            return loss, radii
-        rc = lib.gsr_track_transform_fwd(P, mw.data_ptr(), ur.data_ptr(), lo.data_ptr(), ls.data_ptr(), scols,
-                                         cam_rots.data_ptr() + 4 * t, cam_trans.data_ptr() + 4 * t, T, w2c.data_ptr(),
-                                         means.data_ptr(), rot.data_ptr(), dcol.data_ptr(), opac.data_ptr(),
-                                         scales.data_ptr(), _stream(mw))
-        _check(rc, "track_transform_fwd")
-        empty = torch.Tensor([])
-        if seed is not None and capacity > 0:  # static mode, static seed: loss + gradient images in the render epilogue
-            seed = _f32c(seed, "seed")
-            scratch = _scratch(mw, lib.gsr_track_forward_scratch_floats(W, H))
-            (n, im, ds, radii, geom, binning, img, _, loss, dim, dds) = _C.track_forward_dual_static(
-                cam, means, rgb, dcol, opac, scales, rot, capacity, status, gt_im, gt_d, cfg.sil_thres, cfg.w_im,
-                cfg.w_depth, seed, scratch, terms=terms)
-            ctx.pre = (dim, dds, seed)
-            ctx.save_for_backward(cam_rots, cam_trans, mw, ur, means, rot, dcol, scales, rgb, radii, geom, binning,
-                                  img, im, ds, gt_im, gt_d, w2c)
-            ctx.meta = (t, T, scols, int(n), cam, cfg)
-            ctx.pose_adam = pose_adam
-            ctx.loss_ptr = loss.data_ptr()  # best-candidate selection reads this iteration's loss
-            ctx.log_scales = None
-            ctx.mark_non_differentiable(radii)
-            ctx.set_materialize_grads(False)
-            return loss, radii
-        n, im, ds, radii, geom, binning, img, _ = _C.rasterize_gaussians_dual(
-            cam.bg, means, rgb, dcol, opac, scales, rot, cam.scale_modifier, empty, cam.viewmatrix, cam.projmatrix,
-            cam.tanfovx, cam.tanfovy, cam.image_height, cam.image_width, empty, cam.sh_degree, cam.campos,
-            cam.prefiltered, capacity=capacity, status=status)
-        loss = torch.empty((), **f32)
-        scratch = _scratch(mw, lib.gsr_track_scratch_floats(H * W))
-        dim = dds = None
-        if seed is not None:  # static loss seed: the loss gradient images in the same pass
-            seed = _f32c(seed, "seed")
-            dim, dds = torch.empty_like(im), torch.empty_like(ds)
-            ctx.pre = (dim, dds, seed)
-        _track_l1(H, W, im, ds, gt_im, gt_d, cfg.sil_thres, cfg.w_im, cfg.w_depth, seed, loss, terms, dim, dds,
-                  scratch)
+        else:
+            empty = torch.Tensor([])
+            n, im, ds, radii, geom, binning, img, _ = _C.rasterize_gaussians_dual(
+                cam.bg, means, rgb, dcol, opac, scales, rot, cam.scale_modifier, empty, cam.viewmatrix,
+                cam.projmatrix, cam.tanfovx, cam.tanfovy, cam.image_height, cam.image_width, empty, cam.sh_degree,
+                cam.campos, cam.prefiltered, capacity=capacity, status=status)
+            loss = torch.empty((), **f32)
+            scratch = _scratch(mw, lib.gsr_track_scratch_floats(H * W))
+            dim = dds = None
+            if seed is not None:  # static loss seed: the loss gradient images in the same pass
+                dim, dds = torch.empty_like(im), torch.empty_like(ds)
+            _track_l1(H, W, im, ds, gt_im, gt_d, cfg.sil_thres, cfg.w_im, cfg.w_depth, seed, loss, terms, dim, dds,
+                      scratch)
+        ctx.pre = (dim, dds, seed) if seed is not None else None
+        ctx.records = records
         ctx.save_for_backward(cam_rots, cam_trans, mw, ur, means, rot, dcol, scales, rgb, radii, geom, binning, img,
                               im, ds, gt_im, gt_d, w2c)
         ctx.meta = (t, T, scols, int(n), cam, cfg)
         ctx.pose_adam = pose_adam
-        ctx.loss_ptr = loss.data_ptr()
-        ctx.log_scales = None
+        ctx.loss_ptr = loss.data_ptr()  # best-candidate selection reads this iteration's loss
+        ctx.log_scales = log_scales
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)
         return loss, radii
@@ -633,30 +618,23 @@ class _TrackIteration(torch.autograd.Function):
             if im is None:
                 raise RuntimeError("tracking_iteration(images=False) rendered without storing its images: "
                                    "backpropagate the static loss seed it was given")
-            H, W = cam.image_height, cam.image_width
-            g = g.contiguous()
-            dim, dds = torch.empty_like(im), torch.empty_like(ds)
-            rc = lib.gsr_track_l1_bwd(H, W, im.data_ptr(), ds.data_ptr(), gt_im.data_ptr(), gt_d.data_ptr(),
-                                      float(cfg.sil_thres), float(cfg.w_im), float(cfg.w_depth), g.data_ptr(),
-                                      dim.data_ptr(), dds.data_ptr(), _stream(im))
-            _check(rc, "track_l1_bwd")
-        P = mw.shape[0]
-        scratch = _scratch(mw, lib.gsr_track_backward_scratch_floats(P))
+            dim, dds = _l1_bwd(im, ds, gt_im, gt_d, cfg.sil_thres, cfg.w_im, cfg.w_depth, g)
+        scratch = _scratch(mw, lib.gsr_track_backward_scratch_floats(mw.shape[0]))
         opt = ctx.pose_adam
-        rot_in = rot  # the rendered (camera-frame) rotations: their gradient feeds the pose (anisotropic maps)
-        if opt is not None:
-            _C.track_backward_dual(cam, means, radii, rgb, dcol, scales, rot_in, dim, dds, geom, n, binning, img, mw,
-                                   ur, scols, cam_rots.data_ptr() + 4 * t, cam_trans.data_ptr() + 4 * t, T, w2c,
-                                   scratch, adam=(opt.lr_q, opt.lr_t, float(opt.betas[0]), float(opt.betas[1]),
-                                                  opt.eps, opt.state), track=opt.track(ctx.loss_ptr),
-                                   log_scales=ctx.log_scales, records=records)
-            return nones
-        dq, dt = torch.zeros_like(cam_rots), torch.zeros_like(cam_trans)
-        _C.track_backward_dual(cam, means, radii, rgb, dcol, scales, rot_in, dim, dds, geom, n, binning, img, mw, ur,
-                               scols, cam_rots.data_ptr() + 4 * t, cam_trans.data_ptr() + 4 * t, T, w2c, scratch,
-                               dq_ptr=dq.data_ptr() + 4 * t, dt_ptr=dt.data_ptr() + 4 * t, log_scales=ctx.log_scales,
-                               records=records)
-        return (dq, dt) + (None,) * 12
+        adam = track = dq_ptr = dt_ptr = None
+        if opt is not None:  # the Adam step on the pose in place: no gradient comes back
+            grads = nones
+            adam = (opt.lr_q, opt.lr_t, float(opt.betas[0]), float(opt.betas[1]), opt.eps, opt.state)
+            track = opt.track(ctx.loss_ptr)
+        else:
+            dq, dt = torch.zeros_like(cam_rots), torch.zeros_like(cam_trans)
+            grads = (dq, dt) + (None,) * 12
+            dq_ptr, dt_ptr = _pose_cols(dq, dt, t)
+        # (rot: the rendered, camera-frame rotations -- their gradient feeds the pose on anisotropic maps)
+        _C.track_backward_dual(cam, means, radii, rgb, dcol, scales, rot, dim, dds, geom, n, binning, img, mw, ur,
+                               scols, *_pose_cols(cam_rots, cam_trans, t), T, w2c, scratch, adam=adam, dq_ptr=dq_ptr,
+                               dt_ptr=dt_ptr, track=track, log_scales=ctx.log_scales, records=records)
+        return grads
 
 
 def tracking_iteration(params: dict, curr: dict, time_idx: int, cfg, pose_adam: PoseAdam | None = None,
@@ -705,12 +683,7 @@ class _DualRenderL1(torch.autograd.Function):
         if g.data_ptr() == ctx.pre[2].data_ptr():
             dim, dds = ctx.pre[0], ctx.pre[1]
         else:
-            g = g.contiguous()
-            dim, dds = torch.empty_like(im), torch.empty_like(ds)
-            rc = lib.gsr_track_l1_bwd(st.image_height, st.image_width, im.data_ptr(), ds.data_ptr(), gt_im.data_ptr(),
-                                      gt_d.data_ptr(), float(cfg.sil_thres), float(cfg.w_im), float(cfg.w_depth),
-                                      g.data_ptr(), dim.data_ptr(), dds.data_ptr(), _stream(im))
-            _check(rc, "track_l1_bwd")
+            dim, dds = _l1_bwd(im, ds, gt_im, gt_d, cfg.sil_thres, cfg.w_im, cfg.w_depth, g)
         nd = ctx.needs_input_grad  # (means3D, colors, colors2, opacities, scales, rotations, ...)
         needs = (False, nd[1], nd[2], nd[3], nd[0], False, False, nd[4], nd[5])
         empty = torch.Tensor([])
@@ -728,3 +701,26 @@ def dual_render_tracking_l1(means3D, colors, colors2, opacities, scales, rotatio
     tracking_l1's."""
     return _DualRenderL1.apply(means3D, colors, colors2, opacities, scales, rotations, raster_settings, int(capacity),
                                status, gt_im, gt_depth, cfg, seed, terms)
+
+
+def probe_num_rendered(params: dict, curr_data: dict, time_idx: int, color_key: str | None = None) -> tuple[int, int]:
+    """(num_rendered, longest tile list) of a frame at its current pose (eager, synchronous): what the captured
+    loops (GraphTracker, GraphMapper) size their static binning capacity from.  color_key: None probes with the
+    tracking transform and rgb_colors; the mapper gives its map's colour key ("shs" or "rgb_colors") and the
+    mapping transform runs."""
+    from . import _C
+    from .layout import views
+    cam, empty, w2c = curr_data["cam"], torch.Tensor([]), curr_data["w2c"]
+    with torch.no_grad():
+        if color_key is None:
+            (means, rots, dcol, opac, scales), col = track_transform(params, time_idx, w2c), params["rgb_colors"]
+        else:
+            means, rots, dcol, opac, scales, col = map_transform(params, time_idx, w2c, color_key)
+        sh, colors = (col, empty) if color_key == "shs" else (empty, col)
+        out = _C.rasterize_gaussians_dual(cam.bg, means, colors, dcol, opac, scales, rots, cam.scale_modifier, empty,
+                                          cam.viewmatrix, cam.projmatrix, cam.tanfovx, cam.tanfovy, cam.image_height,
+                                          cam.image_width, sh, cam.sh_degree, cam.campos, cam.prefiltered)
+        n, img, binning = out[0], out[6], out[5]
+        r = views(img, binning, cam.image_width, cam.image_height, n)["ranges"]
+        longest = int((r[:, 1] - r[:, 0]).max().item()) if r.numel() else 0
+    return int(n), longest

@@ -46,30 +46,16 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _C
-from .glue import MapAdam, map_transform
-from .layout import views
+from . import _devcall, glue
+from .glue import MapAdam
 from .slam import MappingConfig, _get_loss_mapping_fused, color_key, fused_mapping_eligible
 
-TILE_SORT_CAP = 4096  # longest tile list the static mode handles (render_fwd's per-tile sort)
 GAUSS_KEYS = ("means3D", "unnorm_rotations", "logit_opacities", "log_scales")
 
 
 def probe_num_rendered(params, curr_data, time_idx) -> tuple[int, int]:
     """(num_rendered, longest tile list) of a keyframe at its current pose (eager, synchronous)."""
-    cam = curr_data["cam"]
-    key = color_key(params)
-    with torch.no_grad():
-        means, rots, dcol, opac, scales, col = map_transform(params, time_idx, curr_data["w2c"], key)
-        sh, colors = (col, torch.Tensor([])) if key == "shs" else (torch.Tensor([]), col)
-        out = _C.rasterize_gaussians_dual(cam.bg, means, colors, dcol, opac, scales, rots, cam.scale_modifier,
-                                          torch.Tensor([]), cam.viewmatrix, cam.projmatrix, cam.tanfovx, cam.tanfovy,
-                                          cam.image_height, cam.image_width, sh, cam.sh_degree, cam.campos,
-                                          cam.prefiltered)
-        n, img, binning = out[0], out[6], out[5]
-        r = views(img, binning, cam.image_width, cam.image_height, n)["ranges"]
-        longest = int((r[:, 1] - r[:, 0]).max().item()) if r.numel() else 0
-    return int(n), longest
+    return glue.probe_num_rendered(params, curr_data, time_idx, color_key(params))
 
 
 class GraphMapper:
@@ -99,11 +85,8 @@ class GraphMapper:
                 raise RuntimeError("alive: uint8 [P] on the parameters' device")
             self.alive = alive
         if capacity is None:
-            probes = [probe_num_rendered(params, kf, kf["id"]) for kf in keyframes]
-            longest = max(p[1] for p in probes)
-            if longest > TILE_SORT_CAP:
-                raise RuntimeError(f"a tile list of {longest} > {TILE_SORT_CAP}: use the eager (synchronous) path")
-            capacity = max(1, int(headroom * max(p[0] for p in probes)) + int(min_extra))
+            capacity = _devcall.capacity_from_probes([probe_num_rendered(params, kf, kf["id"]) for kf in keyframes],
+                                                     headroom, min_extra)
         self.capacity = int(capacity)
         self.iters = int(iters_per_graph)
         self.rng = np.random if seed is None else np.random.RandomState(seed)
@@ -352,9 +335,7 @@ class GraphMapper:
     def overflowed(self) -> bool:
         """True if any iteration since the last reset_status() exceeded the binning capacity, or the last
         replay's optimizer halted (one host sync)."""
-        st = self.status.cpu()
-        return bool((st[:, 0] > self.capacity).any() or (st[:, 2] > TILE_SORT_CAP).any() or (st[:, 1] != 0).any()
-                    or self.adam.halted())
+        return _devcall.status_overflowed(self.status, self.capacity) or self.adam.halted()
 
     def num_rendered(self) -> list[int]:
         return [int(x) for x in self.status[:, 0].cpu()]

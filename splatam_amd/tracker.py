@@ -40,12 +40,9 @@ from __future__ import annotations
 
 import torch
 
-from . import _C
-from .layout import views
-from .rasterizer import GaussianRasterizationSettings
+from ._devcall import TILE_SORT_CAP, capacity_from_probes, status_overflowed  # noqa: F401
+from .glue import probe_num_rendered
 from .slam import TrackingConfig, _get_loss_tracking_fused, fused_eligible
-
-TILE_SORT_CAP = 4096  # longest tile list the static mode handles (render_fwd's per-tile sort)
 
 
 def run_frame(tracker, num_iters: int, depth_loss_thres: float | None = None) -> int:
@@ -68,22 +65,6 @@ def run_frame(tracker, num_iters: int, depth_loss_thres: float | None = None) ->
     return ran
 
 
-def probe_num_rendered(params, curr_data, time_idx) -> tuple[int, int]:
-    """(num_rendered, longest tile list) of the frame at the current pose (eager, synchronous)."""
-    from .glue import track_transform
-    cam: GaussianRasterizationSettings = curr_data["cam"]
-    with torch.no_grad():
-        means, rots, dcol, opac, scales = track_transform(params, time_idx, curr_data["w2c"])
-        out = _C.rasterize_gaussians_dual(cam.bg, means, params["rgb_colors"], dcol, opac, scales, rots,
-                                          cam.scale_modifier, torch.Tensor([]), cam.viewmatrix, cam.projmatrix,
-                                          cam.tanfovx, cam.tanfovy, cam.image_height, cam.image_width,
-                                          torch.Tensor([]), cam.sh_degree, cam.campos, cam.prefiltered)
-        n, img, binning = out[0], out[6], out[5]
-        r = views(img, binning, cam.image_width, cam.image_height, n)["ranges"]
-        longest = int((r[:, 1] - r[:, 0]).max().item()) if r.numel() else 0
-    return int(n), longest
-
-
 class GraphTracker:
     def __init__(self, params: dict, curr_data: dict, time_idx: int, iters_per_graph: int = 20,
                  cfg: TrackingConfig = TrackingConfig(), lrs=(0.0004, 0.002), headroom: float = 1.5,
@@ -100,10 +81,7 @@ class GraphTracker:
         self.alive = alive
         dev = params["means3D"].device
         if capacity is None:  # (capacity: the binning capacity given, e.g. for a map that grows between frames)
-            n, longest = probe_num_rendered(params, curr_data, time_idx)
-            if longest > TILE_SORT_CAP:
-                raise RuntimeError(f"a tile list of {longest} > {TILE_SORT_CAP}: use the eager (synchronous) path")
-            capacity = max(1, int(headroom * n) + int(min_extra))
+            capacity = capacity_from_probes([probe_num_rendered(params, curr_data, time_idx)], headroom, min_extra)
         self.capacity = int(capacity)
         self.iters = int(iters_per_graph)
         self.status = torch.zeros(self.iters, 4, dtype=torch.int32, device=dev)
@@ -239,8 +217,7 @@ class GraphTracker:
 
     def overflowed(self) -> bool:
         """True if any iteration since the last reset_status() exceeded the binning capacity (one host sync)."""
-        st = self.status.cpu()
-        return bool((st[:, 0] > self.capacity).any() or (st[:, 2] > TILE_SORT_CAP).any() or (st[:, 1] != 0).any())
+        return status_overflowed(self.status, self.capacity)
 
     def num_rendered(self) -> list[int]:
         """Per captured iteration: the largest num_rendered since the last reset_status()."""
