@@ -18,9 +18,14 @@
 #include <utility>
 
 #include "gsr_chain.h"
+#include "gsr_clock.h"
 #include "gsr_diag.h"
 #include "gsr_glue_common.h"
+#include "gsr_launch.h"
+#include "gsr_layout.h"
+#include "gsr_math.h"
 #include "gsr_render_fwd.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 
@@ -758,10 +763,20 @@ hipError_t launch_render_track(const Camera& cam, const uint2* ranges, uint64_t*
 template <bool DUAL, bool OPAC, bool COL1, bool COL2, int Q2 = 3>
 static auto bwd_variant() { return render_bwd_kernel<DUAL, OPAC, COL1, COL2, Q2>; }
 
+// (need, dual) decoded into the optional per-pair sums of the variant: opacity, colours, second colours and
+// the second image's gradient channels (1 or 3; 3 without a second image)
+struct BwdTerms {
+    bool op, c1, c2;
+    int q2;
+};
+static BwdTerms bwd_terms(unsigned need, bool dual) {
+    return {(need & NEED_OPACITY) != 0, (need & NEED_COLORS) != 0, dual && (need & NEED_COLORS2),
+            (dual && (need & NEED_DL2_CH0_ONLY)) ? 1 : 3};
+}
+
 // The variant launch_render_bwd picks for (need, dual) and its record layout.
 RecLayout bwd_rec_layout(unsigned need, bool dual) {
-    const bool op = need & NEED_OPACITY, c1 = need & NEED_COLORS, c2 = dual && (need & NEED_COLORS2);
-    const int q2 = (dual && (need & NEED_DL2_CH0_ONLY)) ? 1 : 3;
+    const auto [op, c1, c2, q2] = bwd_terms(need, dual);
     RecLayout L;
     int nv = 5;
     L.o_op = op ? nv : -1;
@@ -779,8 +794,8 @@ hipError_t launch_render_bwd(const Camera& cam, const uint2* ranges, const uint6
                              const float* final_T, const uint32_t* n_contrib, const float* dL_dpix,
                              const float* colors2, const float* dL_dpix2, unsigned need, float* inst,
                              BwdGuard guard, hipStream_t s, unsigned long long* clk) {
-    const bool op = need & NEED_OPACITY, c1 = need & NEED_COLORS, c2 = colors2 && (need & NEED_COLORS2);
-    const bool q1 = need & NEED_DL2_CH0_ONLY;
+    const auto [op, c1, c2, q2] = bwd_terms(need, colors2 != nullptr);
+    const bool q1 = q2 == 1;  // (only with a second image)
     auto k = bwd_variant<false, true, true, false>();
     if (!colors2) {
         k = op ? (c1 ? bwd_variant<false, 1, 1, 0>() : bwd_variant<false, 1, 0, 0>())

@@ -31,6 +31,10 @@
 #include <cstdlib>
 
 #include "gsr_chain.h"
+#include "gsr_launch.h"
+#include "gsr_layout.h"
+#include "gsr_math.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 

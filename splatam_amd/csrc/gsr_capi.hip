@@ -18,7 +18,11 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_glue.h"
+#include "gsr_adam.h"
+#include "gsr_errors.h"
 #include "gsr_host.h"
+#include "gsr_launch.h"
+#include "gsr_layout.h"
 
 using namespace gsr;
 
@@ -1218,15 +1222,10 @@ int gsr_backward_dual_sh_adam(const gsr_settings* settings, const gsr_gaussians*
         return fail(GSR_ERR_INVALID_ARG, "backward_dual_sh_adam: SH colours and the colour group's state required");
     // the scalars exactly as gsr_map_transform_bwd_adam forms them (python floats -> float)
     ShAdam sa;
-    const double bc1 = 1.0 - pow(sh_adam->beta1, (double)sh_adam->step);
     sa.m = sh_adam->exp_avg[4];
     sa.v = sh_adam->exp_avg_sq[4];
-    sa.ss = (float)(-sh_adam->lr[4] / bc1);
-    sa.w1 = (float)(1.0 - sh_adam->beta1);
-    sa.beta2 = (float)sh_adam->beta2;
-    sa.omb2 = (float)(1.0 - sh_adam->beta2);
-    sa.bc2_sqrt = (float)sqrt(1.0 - pow(sh_adam->beta2, (double)sh_adam->step));
-    sa.eps = (float)sh_adam->eps;
+    sa.ss = (float)(-sh_adam->lr[4] / adam_bc1(sh_adam->beta1, sh_adam->step));
+    sa.c = adam_coef(sh_adam->beta1, sh_adam->beta2, sh_adam->eps, sh_adam->step);
     sa.halted = sh_adam->halted;
     // sa.guard / sa.cap: the forward's own counters (Backward::power1); sh_adam->status is not read
     BwdCall c = bwd_call(settings, gaussians, radii, num_rendered, geom_buffer, binning_buffer, image_buffer);

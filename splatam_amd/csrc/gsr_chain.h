@@ -1,7 +1,8 @@
 // gsr_chain.h -- per-Gaussian backward chain shared by the power-1 and the
 // backward_power != 1 pipelines (gsr_backward.hip, gsr_backward_power.hip).
 #pragma once
-#include "gsr_common.h"
+#include "gsr_layout.h"
+#include "gsr_math.h"
 
 namespace gsr {
 

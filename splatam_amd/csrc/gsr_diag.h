@@ -9,7 +9,7 @@
 //   GSR_PHASE     per-wave s_memtime cycles per render_bwd phase: [0] prologue, [1] batch staging + barrier,
 //                 [2] row / slot list build, [3] row walk, [4] barrier after the walk, [5] entry totals +
 //                 record stores, [6] barrier after the totals, [7] batches x waves
-//   GSR_WGTIME    per-workgroup [start, end, HW_ID, XCC_ID] of the render kernels (gsr_common.h)
+//   GSR_WGTIME    per-workgroup [start, end, HW_ID, XCC_ID] of the render kernels (gsr_clock.h)
 //   GSR_ABLATE / GSR_FWD_ABLATE  timing ablations of the backward / forward render (results invalid);
 //                 GSR_ABLATE is read through kAblate
 //   GSR_DUP_PHASE one render phase run twice, for a VALU census by SQ counters (results unchanged)
@@ -17,7 +17,7 @@
 // no code, and an A/B of two implementations is built from two revisions (build.build_from_rev), not from a
 // macro in the sources.
 #pragma once
-#include "gsr_common.h"
+#include "gsr_clock.h"
 
 #ifndef GSR_STEPSTAT
 #define GSR_STEPSTAT 0

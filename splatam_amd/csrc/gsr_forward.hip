@@ -12,9 +12,14 @@
 //               LDS batches, block-wide early exit
 #include <cstdlib>
 
-#include "gsr_glue_common.h"  // (includes gsr_common.h) track_xform_compute / _store: the transform-fused preprocess
+#include "gsr_clock.h"
 #include "gsr_diag.h"
+#include "gsr_glue_common.h"  // track_xform_compute / _store: the transform-fused preprocess
+#include "gsr_launch.h"
+#include "gsr_layout.h"
+#include "gsr_math.h"
 #include "gsr_render_fwd.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 
@@ -1199,7 +1204,7 @@ hipError_t launch_gather_ids(const uint32_t* vals, const uint32_t* gid, uint64_t
 // DUAL: a second colour set (colors2, e.g. SplaTAM's [z, 1, z^2]) is composited
 // in the same pass -- same alpha / T / termination, so each output is bitwise
 // the image a separate call would produce.
-// L1 (with DUAL): the tracking loss epilogue of TrackL1 (gsr_common.h).
+// L1 (with DUAL): the tracking loss epilogue of TrackL1 (gsr_launch.h).
 template <bool DUAL, bool L1 = false>
 __global__ void __launch_bounds__(TILE_PIX, 5)
 render_fwd_kernel(Camera cam, const uint2* __restrict__ ranges, PointEntry* __restrict__ point_list,

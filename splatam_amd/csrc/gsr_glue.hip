@@ -25,7 +25,10 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_glue.h"
+#include "gsr_errors.h"
 #include "gsr_glue_common.h"
+#include "gsr_layout.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 namespace {

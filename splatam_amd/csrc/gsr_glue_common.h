@@ -5,7 +5,9 @@
 #pragma once
 #include <math.h>
 
-#include "gsr_common.h"
+#include "gsr_adam.h"
+#include "gsr_layout.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 namespace {
@@ -169,16 +171,11 @@ struct PoseAdam {  // torch.optim.Adam (no weight decay, no amsgrad) on the fram
     float* best = nullptr;            // [min loss, q 4, t 3]
 };
 
-// torch/optim/adam.py (foreach form): exp_avg.lerp_(g, 1-b1); exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2);
-// p.addcdiv_(exp_avg, sqrt(exp_avg_sq) / sqrt(1 - b2^s) + eps, -lr / (1 - b1^s)), the scalars
-// formed in double like torch's python floats.
+// torch.optim.Adam's element update in the contracted form (adam_elem, gsr_adam.h), the scalars formed in
+// double like torch's python floats; beta2 is rounded to float here, on the device.
 __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float neg_step, const PoseAdam& a,
                                             float bc2_sqrt) {
-    m = m + a.w1 * (g - m);                      // exp_avg.lerp_(g, 1 - beta1)
-    v = v * (float)a.beta2;                      // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
-    v = v + a.omb2 * g * g;
-    const float denom = sqrtf(v) / bc2_sqrt + a.eps;
-    p = p + neg_step * (m / denom);
+    adam_elem(p, g, m, v, neg_step, AdamCoef{a.w1, (float)a.beta2, a.omb2, bc2_sqrt, a.eps});
 }
 
 // beta^n for the Adam bias corrections, formed in double like torch's python floats: by

@@ -1,7 +1,7 @@
 // gsr_host.h -- host-only helpers of the C entry points: shared by gsr_capi.hip (orchestration) and
 // gsr_timing.hip (stage timing), included by nothing else.
 #pragma once
-#include "gsr_common.h"
+#include "gsr_layout.h"
 
 namespace gsr {
 

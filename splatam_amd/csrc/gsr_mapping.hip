@@ -30,7 +30,11 @@
 
 #include "../../include/gsr.h"
 #include "../../include/gsr_glue.h"
+#include "gsr_adam.h"
+#include "gsr_errors.h"
 #include "gsr_glue_common.h"
+#include "gsr_layout.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 namespace {
@@ -320,23 +324,12 @@ struct AdamArgs {
     float step_size[ADAM_MAX];   // -lr / (1 - beta1^step)   (double on the host, like torch's python floats)
     int blk0[ADAM_MAX + 1];      // first workgroup of each tensor
     int nt;
-    float w1;                    // 1 - beta1 (lerp weight)
-    float beta2, omb2;           // beta2, 1 - beta2
-    float bc2_sqrt, eps;
+    AdamCoef c;
     int vec;                     // bit t: tensor t is 16-byte aligned in all four streams
 };
 
-// torch/optim/adam.py _multi_tensor_adam (capturable=False, no weight decay, no
-// amsgrad): m.lerp_(g, 1 - b1); v.mul_(b2).addcmul_(g, g, 1 - b2);
-// p.addcdiv_(m, sqrt(v) / sqrt(bc2) + eps, -lr / bc1).
-__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float ss, const AdamArgs& a) {
-    m = m + a.w1 * (g - m);
-    v = v * a.beta2;
-    v = v + a.omb2 * g * g;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    p = p + ss * (m / denom);
-}
-
+// torch/optim/adam.py _multi_tensor_adam (capturable=False, no weight decay, no amsgrad) through adam_elem,
+// the contracted element form of gsr_adam.h
 __global__ void __launch_bounds__(ADAM_BLOCK) adam_step_kernel(AdamArgs a) {
     int t = 0;
     while (t + 1 < a.nt && (int)blockIdx.x >= a.blk0[t + 1]) t++;
@@ -355,21 +348,21 @@ __global__ void __launch_bounds__(ADAM_BLOCK) adam_step_kernel(AdamArgs a) {
                 float4 P4 = *reinterpret_cast<const float4*>(p + i), G4 = ld_stream(reinterpret_cast<const float4*>(g + i));
                 float4 M4 = ld_stream(reinterpret_cast<const float4*>(m + i));
                 float4 V4 = ld_stream(reinterpret_cast<const float4*>(v + i));
-                adam_elem(P4.x, G4.x, M4.x, V4.x, ss, a);
-                adam_elem(P4.y, G4.y, M4.y, V4.y, ss, a);
-                adam_elem(P4.z, G4.z, M4.z, V4.z, ss, a);
-                adam_elem(P4.w, G4.w, M4.w, V4.w, ss, a);
+                adam_elem(P4.x, G4.x, M4.x, V4.x, ss, a.c);
+                adam_elem(P4.y, G4.y, M4.y, V4.y, ss, a.c);
+                adam_elem(P4.z, G4.z, M4.z, V4.z, ss, a.c);
+                adam_elem(P4.w, G4.w, M4.w, V4.w, ss, a.c);
                 st_stream(reinterpret_cast<float4*>(p + i), P4);
                 st_stream(reinterpret_cast<float4*>(m + i), M4);
                 st_stream(reinterpret_cast<float4*>(v + i), V4);
             } else {
-                for (long long e = i; e < n; e++) adam_elem(p[e], g[e], m[e], v[e], ss, a);
+                for (long long e = i; e < n; e++) adam_elem(p[e], g[e], m[e], v[e], ss, a.c);
             }
         }
     } else {
         for (int k = 0; k < 16; k++) {
             const long long i = base + (long long)k * ADAM_BLOCK + threadIdx.x;
-            if (i < n) adam_elem(p[i], g[i], m[i], v[i], ss, a);
+            if (i < n) adam_elem(p[i], g[i], m[i], v[i], ss, a.c);
         }
     }
 }
@@ -380,7 +373,7 @@ struct MapAdam {  // the mapping optimizer's state, applied in place (NULL p: wr
     float* m[5];
     float* v[5];
     float step_size[5];
-    float w1, beta2, omb2, bc2_sqrt, eps;
+    AdamCoef c;
     const uint32_t* guard;  // status row of the iteration's forward: skip the step on an overflow
     uint32_t cap;
     uint32_t* halted;       // gsr_map_adam.halted (sticky skip), or nullptr
@@ -388,7 +381,7 @@ struct MapAdam {  // the mapping optimizer's state, applied in place (NULL p: wr
 
 __device__ __forceinline__ float adam_apply(float* p, float g, float* m, float* v, float ss, const MapAdam& a) {
     float mm = ld_stream(m), vv = ld_stream(v);
-    const float np = adam_update_elem(*p, g, mm, vv, ss, a.w1, a.beta2, a.omb2, a.bc2_sqrt, a.eps);
+    const float np = adam_update_elem(*p, g, mm, vv, ss, a.c);
     st_stream(m, mm);
     st_stream(v, vv);
     st_stream(p, np);
@@ -411,7 +404,7 @@ __device__ __forceinline__ void adam_apply_n(float* p, const float* g, float* m,
 #pragma unroll
     for (int k = 0; k < N; k++) {
         float mm = mv[k], v2 = vv[k];
-        const float np = adam_update_elem(pv[k], g[k], mm, v2, ss, a.w1, a.beta2, a.omb2, a.bc2_sqrt, a.eps);
+        const float np = adam_update_elem(pv[k], g[k], mm, v2, ss, a.c);
         st_stream(m + k * stride, mm);
         st_stream(v + k * stride, v2);
         st_stream(p + k * stride, np);
@@ -540,8 +533,7 @@ map_transform_bwd_kernel(int P, const float* ur, const float* lo, const float* l
 #pragma unroll
     for (int e = 0; e < 11; e++) {
         const float ss = adam.step_size[e < 3 ? 0 : (e < 7 ? 1 : (e < 8 ? 2 : 3))];
-        pv[e] = adam_update_elem(pv[e], gv[e], mv[e], vv[e], ss, adam.w1, adam.beta2, adam.omb2, adam.bc2_sqrt,
-                                 adam.eps);
+        pv[e] = adam_update_elem(pv[e], gv[e], mv[e], vv[e], ss, adam.c);
     }
     // stores grouped by array (adjacent elements of one array in a row), so they merge into
     // dwordx3 / dwordx4 stores: interleaving p / m / v stores (possibly aliasing) kept them dwords
@@ -583,16 +575,6 @@ int map_loss_rows(int H, int W) {
 int map_loss_blocks(int H, int W, dim3& grid, int rows) {
     grid = dim3((W + SS_TW - 1) / SS_TW, (H + rows - 1) / rows, 3);
     return (int)(grid.x * grid.y * grid.z);
-}
-
-// torch forms these scalars from python floats (double) and rounds them to float in the kernels
-void fill_adam_common(double beta1, double beta2, double eps, int step, float& w1, float& b2, float& omb2,
-                      float& bc2_sqrt, float& e) {
-    w1 = (float)(1.0 - beta1);
-    b2 = (float)beta2;
-    omb2 = (float)(1.0 - beta2);
-    bc2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
-    e = (float)eps;
 }
 
 // prune_gaussians' removal test (utils/slam_external.py:174-181) as an in-place mask update: one lane per
@@ -697,14 +679,14 @@ int gsr_map_transform_bwd_adam(int P, float* means_world, float* unnorm_rot, flo
             if (k < 4 || dL_dcolors) return fail(GSR_ERR_INVALID_ARG, "map_transform_bwd_adam: null optimizer state");
     MapAdam a{};
     float* ps[5] = {means_world, unnorm_rot, logit_opac, log_scales, colors};
-    const double bc1 = 1.0 - pow(adam->beta1, (double)adam->step);
+    const double bc1 = adam_bc1(adam->beta1, adam->step);
     for (int k = 0; k < 5; k++) {
         a.p[k] = ps[k];
         a.m[k] = adam->exp_avg[k];
         a.v[k] = adam->exp_avg_sq[k];
         a.step_size[k] = (float)(-adam->lr[k] / bc1);
     }
-    fill_adam_common(adam->beta1, adam->beta2, adam->eps, adam->step, a.w1, a.beta2, a.omb2, a.bc2_sqrt, a.eps);
+    a.c = adam_coef(adam->beta1, adam->beta2, adam->eps, adam->step);
     a.guard = adam->status;
     a.cap = adam->capacity;
     a.halted = adam->halted;
@@ -732,7 +714,7 @@ int gsr_adam_step(int n_tensors, const gsr_adam_tensor* tensors, int step, doubl
     if (n_tensors < 0 || n_tensors > ADAM_MAX || step < 1 || (n_tensors > 0 && !tensors))
         return fail(GSR_ERR_INVALID_ARG, "adam_step: bad arguments (at most 16 tensors, step >= 1)");
     AdamArgs a{};
-    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc1 = adam_bc1(beta1, step);
     int blocks = 0, nt = 0;
     for (int t = 0; t < n_tensors; t++) {
         const gsr_adam_tensor& x = tensors[t];
@@ -750,7 +732,7 @@ int gsr_adam_step(int n_tensors, const gsr_adam_tensor* tensors, int step, doubl
     if (nt == 0) return GSR_OK;
     a.blk0[nt] = blocks;
     a.nt = nt;
-    fill_adam_common(beta1, beta2, eps, step, a.w1, a.beta2, a.omb2, a.bc2_sqrt, a.eps);
+    a.c = adam_coef(beta1, beta2, eps, step);
     hipLaunchKernelGGL(adam_step_kernel, dim3(blocks), dim3(ADAM_BLOCK), 0, (hipStream_t)stream, a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? GSR_OK : hip_fail(e, "adam_step");

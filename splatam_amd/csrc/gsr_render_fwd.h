@@ -2,8 +2,11 @@
 // per-tile sort it starts with: shared by render_fwd_kernel (gsr_forward.hip) and the tracking kernel
 // that runs a tile's forward and backward in one workgroup (render_track_kernel, gsr_backward.hip).
 #pragma once
-#include "gsr_common.h"
 #include "gsr_diag.h"
+#include "gsr_launch.h"
+#include "gsr_layout.h"
+#include "gsr_math.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 

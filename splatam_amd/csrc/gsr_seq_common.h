@@ -3,7 +3,7 @@
 // workgroup's exclusive scan of per-workgroup counts, the workgroup count from wave popcounts and
 // the back-projection of a pixel through the rigid inverse of w2c.
 #pragma once
-#include "gsr_common.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 namespace {

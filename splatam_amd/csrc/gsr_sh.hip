@@ -13,8 +13,13 @@
 //                   dsh (staged in LDS, written as one float4 stream) and the
 //                   view-direction term added to dL/dmeans3D, after gauss_bwd has
 //                   written dL/dcolor into a scratch array.
+#include "gsr_adam.h"
 #include "gsr_chain.h"
 #include "gsr_glue_common.h"
+#include "gsr_launch.h"
+#include "gsr_layout.h"
+#include "gsr_math.h"
+#include "gsr_wave.h"
 
 namespace gsr {
 namespace {
@@ -95,7 +100,7 @@ __device__ __forceinline__ void adam_rows(float* p, float* m, float* v, const fl
     using T = ShTile<NSH>;
     const int total = n * T::ROW;
     auto elem = [&](float& pp, float g, float& mm_, float& vv_) {
-        pp = adam_update_elem(pp, g, mm_, vv_, a.ss, a.w1, a.beta2, a.omb2, a.bc2_sqrt, a.eps);
+        pp = adam_update_elem(pp, g, mm_, vv_, a.ss, a.c);
     };
     const bool vec = T::ROW % 4 == 0 && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) |
                                           reinterpret_cast<uintptr_t>(v)) & 15u) == 0;
@@ -162,7 +167,7 @@ __device__ __forceinline__ void adam_rows_lds(float* p, float* m, float* v, cons
     using T = ShTile<NSH>;
     const int total = n * T::ROW;
     auto elem = [&](float& pp, float g, float& mm_, float& vv_) {
-        pp = adam_update_elem(pp, g, mm_, vv_, a.ss, a.w1, a.beta2, a.omb2, a.bc2_sqrt, a.eps);
+        pp = adam_update_elem(pp, g, mm_, vv_, a.ss, a.c);
     };
     float4* p4 = reinterpret_cast<float4*>(p);
     float4* m4 = reinterpret_cast<float4*>(m);

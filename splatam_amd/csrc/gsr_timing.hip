@@ -5,6 +5,8 @@
 #include <vector>
 
 #include "../../include/gsr.h"
+#include "gsr_clock.h"
+#include "gsr_errors.h"
 #include "gsr_host.h"
 
 namespace {

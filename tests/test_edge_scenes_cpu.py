@@ -101,7 +101,7 @@ def test_budget_table_matches_sources():
     csrc = os.path.join(ROOT, "splatam_amd", "csrc")
     bwd = open(os.path.join(csrc, "gsr_backward.hip")).read()
     pw = open(os.path.join(csrc, "gsr_backward_power.hip")).read()
-    common = open(os.path.join(csrc, "gsr_common.h")).read()
+    common = open(os.path.join(csrc, "gsr_layout.h")).read()
     BB = int(_define(bwd, "GSR_BWD_BB"))
     WBB = int(_define(bwd, "GSR_BWD_WBB"))
     WBS = int(_define(bwd, "GSR_BWD_WBS"))

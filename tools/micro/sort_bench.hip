@@ -6,7 +6,7 @@
 #include <vector>
 #include <algorithm>
 
-#include "gsr_common.h"
+#include "gsr_layout.h"
 
 namespace gsr {
 hipError_t launch_tile_sort(int ntiles, const uint2* ranges, const uint64_t* keys, uint64_t* point_list,

@@ -28,7 +28,7 @@ def instance_culling(geom, v, W, H, R, P):
     strip) reach alpha >= 1/255 inside power <= 0?  Same math as the render
     kernels (exp of the conic power, min(0.99, o * G))."""
     rr = geom[:16 * 4 * P].view(torch.float32).reshape(P, 16)
-    # render-record form (gsr_common.h): q0 = (x, y, K_AC A, K_AC C), q1 = (K_B B, o, ...)
+    # render-record form (gsr_layout.h): q0 = (x, y, K_AC A, K_AC C), q1 = (K_B B, o, ...)
     k_ac, k_b = -0.5 * 1.4426950408889634, -1.4426950408889634
     x, y, A, C, B, o = rr[:, 0], rr[:, 1], rr[:, 2] / k_ac, rr[:, 3] / k_ac, rr[:, 4] / k_b, rr[:, 5]
     rng = v["ranges"].long()
@@ -57,7 +57,7 @@ def instance_culling(geom, v, W, H, R, P):
         blocks_exact[0] += float(okb.any(2).sum())
         px_ok[0] += float(ok.sum())
         any_tile[sl] = strips[sl].any(1)
-    # strip_mask (gsr_common.h): the alpha ellipse's axis-aligned box against each strip
+    # strip_mask (gsr_math.h): the alpha ellipse's axis-aligned box against each strip
     det = A * C - B * B
     kappa = A * C / det
     tau = torch.log(torch.clamp(255.0 * o, min=1.0)) * (1.001 + 4e-6 * kappa) + 1e-3
