@@ -233,6 +233,23 @@ int gsr_backward_dual(const gsr_settings* settings, const gsr_gaussians* gaussia
                       float* dcolors2, int dl2_channels, gsr_alloc_fn alloc, void* alloc_ctx,
                       void* stream);
 
+/* gsr_backward_dual for the mapping form, with one more output: dmeans2D_color1 [P,3], the means2D gradient
+ * of the FIRST colour set's render alone -- what a separate backward of that render with the same
+ * dL_dout_color writes into its dmeans2D (x, y in NDC units, z written as 0; rows with radius 0, or culled
+ * by an alive mask, are zero).  Gaussian-splatting densification reads this gradient's norm
+ * (scripts/splatam.py:256, utils/slam_external.py:100-104); grads->dmeans2D, when given, still receives the
+ * sum over both renders.  Every other output is bit for bit gsr_backward_dual's.
+ * One render-backward variant serves it, so the call is refused unless it is the mapping form:
+ * dl2_channels == 1, and grads->dopacity, dcolors2 and grads->dcolors (or SH colours in `gaussians`) given.
+ * dmeans2D_color1 must not be NULL and must be 4-byte aligned.  The mapping optimizer's colour step inside
+ * the SH backward (gsr_backward_dual_sh_adam) has no such sibling: step SH colours with gsr_adam_step. */
+int gsr_backward_dual_m2d(const gsr_settings* settings, const gsr_gaussians* gaussians,
+                          const int* radii, const float* colors2, const float* dL_dout_color,
+                          const float* dL_dout_color2, int num_rendered, const void* geom_buffer,
+                          const void* binning_buffer, const void* image_buffer, const gsr_grads* grads,
+                          float* dcolors2, int dl2_channels, float* dmeans2D_color1, gsr_alloc_fn alloc,
+                          void* alloc_ctx, void* stream);
+
 /* Frustum test view_z > 0.001.  Replaces markVisible / checkFrustum
  * (rasterize_points.cu:198-216, rasterizer_impl.cu:54-67,141-153).
  * visible: [P] bytes (0/1, torch.bool layout). */

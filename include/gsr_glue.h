@@ -398,6 +398,18 @@ int gsr_forward_dual_static_xf(const gsr_settings* settings, const gsr_gaussians
                                float* out_color2, float* out_depth, int* radii, gsr_alloc_fn alloc, void* alloc_ctx,
                                void* stream);
 
+/* Gaussian-splatting densification's per-iteration statistics (accumulate_mean2d_gradient,
+ * utils/slam_external.py:100-104, with scripts/splatam.py:349) in one launch, one lane per Gaussian, without
+ * the reference's boolean index and its host read.  For radii[i] > 0:
+ *     accum[i] += sqrtf(gx^2 + gy^2)   with (gx, gy) = dmeans2D[i, 0:2] (dmeans2D is [P,3]),
+ *     denom[i] += 1,
+ *     max_2D_radius[i] = max(max_2D_radius[i], radii[i]);
+ * the other rows are not written.  The norm's operands are scaled by an exact power of two, so it stays
+ * within 2 ulp for denormal gradients too (the plain expression's bits wherever that neither underflows nor
+ * overflows).  dmeans2D is the RGB render's own gradient: gsr_backward_dual_m2d's dmeans2D_color1. */
+int gsr_accumulate_mean2d(int P, const int* radii, const float* dmeans2D, float* accum, float* denom,
+                          float* max_2D_radius, void* stream);
+
 /* torch.optim.Adam (foreach implementation, no weight decay / amsgrad /
  * maximize) over up to 16 float32 tensors in one launch; every tensor shares
  * `step` (>= 1, already incremented) and has its own lr. */

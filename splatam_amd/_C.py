@@ -528,14 +528,20 @@ def rasterize_gaussians_dual(background, means3D, colors, colors2, opacity, scal
 def rasterize_gaussians_dual_backward(background, means3D, radii, colors, colors2, scales, rotations, scale_modifier,
                                       cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                       dL_dout_color2, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer,
-                                      needs=None, dl2_channels=3, sh_adam=None):
+                                      needs=None, dl2_channels=3, sh_adam=None, means2D_color1=False):
     """gsr_backward_dual.  Returns (dmeans2D, dcolors, dcolors2, dopacity, dmeans3D, dcov3D, dsh, dscales,
     drotations); geometric gradients are the sums over both colour sets.  `needs` (9 bools in that
     order, default all) skips the gradients nobody wants: they come back as None and the kernels do
     not form their per-pair sums.  dl2_channels=1 promises dL_dout_color2[1:] == 0 (only the depth
     channel is differentiated): those channels are not read and dcolors2[:, 1:] comes back zero.
     sh_adam: a GsrMapAdam (the mapping optimizer, colour group = index 4, step = the upcoming one): the
-    colour Adam step is applied to `sh` in place (gsr_backward_dual_sh_adam) and dsh comes back None."""
+    colour Adam step is applied to `sh` in place (gsr_backward_dual_sh_adam) and dsh comes back None.
+    means2D_color1: dmeans2D is the FIRST colour set's own means2D gradient instead of the sum over both
+    (gsr_backward_dual_m2d: the mapping form only -- dl2_channels=1, dcolors or SH, dcolors2 and dopacity
+    wanted, no sh_adam)."""
+    if means2D_color1 and sh_adam is not None:
+        raise ValueError("means2D_color1: gsr_backward_dual_sh_adam has no such sibling (step SH colours with "
+                         "glue.FusedAdam)")
     device = means3D.device
     P = means3D.size(0)
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
@@ -561,6 +567,11 @@ def rasterize_gaussians_dual_backward(background, means3D, radii, colors, colors
         radii_c = radii.to(device=device, dtype=torch.int32).contiguous()
         grads = GsrGrads(*[o.data_ptr() if (o is not None and o.numel() > 0) else None for o in out])
         fn, step = lib.gsr_backward_dual, ()
+        if means2D_color1:  # the same tensor comes back as dmeans2D; the sum over both renders is not formed
+            if out[0] is None:
+                raise ValueError("means2D_color1 needs dmeans2D among `needs`")
+            grads.dmeans2D = None
+            fn, step = lib.gsr_backward_dual_m2d, (out[0].data_ptr(),)
         if sh_adam is not None:
             if fr.keep_g[1] is None or fr.keep_g[1].data_ptr() != sh.data_ptr():
                 raise RuntimeError("sh_adam steps the SH coefficients in place: sh must be contiguous float32")

@@ -80,6 +80,11 @@ SIGNATURES = {
     "gsr_backward_dual": (c_int, [ctypes.POINTER(GsrSettings), ctypes.POINTER(GsrGaussians), c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, ctypes.POINTER(GsrGrads),
                                   c_void_p, c_int, ALLOC_FN, c_void_p, c_void_p]),
+    # gsr_backward_dual's arguments with `dmeans2D_color1` behind `dl2_channels`
+    "gsr_backward_dual_m2d": (c_int, [ctypes.POINTER(GsrSettings), ctypes.POINTER(GsrGaussians), c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                      ctypes.POINTER(GsrGrads), c_void_p, c_int, c_void_p, ALLOC_FN, c_void_p,
+                                      c_void_p]),
     "gsr_forward_reuse": (c_int, [ctypes.POINTER(GsrSettings), ctypes.POINTER(GsrGaussians), c_int, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ALLOC_FN, c_void_p,
                                   c_void_p]),
@@ -191,6 +196,7 @@ SIGNATURES = {
     "gsr_forward_dual_static_xf": (c_int, [ctypes.POINTER(GsrSettings), ctypes.POINTER(GsrGaussians), c_void_p,
                                            ctypes.POINTER(GsrTrackXform), c_int, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, ALLOC_FN, c_void_p, c_void_p]),
+    "gsr_accumulate_mean2d": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # include/gsr_glue.h: Fisher scoring glue
     "gsr_points_to_camera": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_fisher_accumulate": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

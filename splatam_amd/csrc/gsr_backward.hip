@@ -116,6 +116,12 @@ constexpr int bwd_batch() { return MOM ? 128 : (NV <= 6 ? GSR_BWD_BB : GSR_BWD_W
 #ifndef GSR_BWD_BS
 #define GSR_BWD_BS (4 * GSR_BWD_BB)  // slot budget of the batches of the variants with <= 6 sums
 #endif
+#ifndef GSR_BWD_M2D_BS
+// slot budget of the M2D1 variant (12 sums per slot): the wide variants' 384 slots, 34.2 KB of LDS per workgroup
+// -- four workgroups per CU, which is what its registers allow anyway (GSR_BWD_M2D_WAVES).  352 slots would fit
+// five (32.7 KB); a batch cut short moves no sum, because an entry lives in one batch
+#define GSR_BWD_M2D_BS GSR_BWD_WBS
+#endif
 // the moment variants (backward_power == 2): 19 / 37 sums per slot; 256 / 128 slots keep 4 workgroups per CU
 template <int NV, int MOM = 0>
 constexpr int bwd_slots() { return MOM == 1 ? 256 : (MOM == 2 ? 128 : (NV <= 6 ? GSR_BWD_BS : GSR_BWD_WBS)); }
@@ -153,8 +159,10 @@ constexpr int bwd_slots() { return MOM == 1 ? 256 : (MOM == 2 ? 128 : (NV <= 6 ?
 //   MOM 1 (colours precomputed, 16 sums): [13, 16) sum (dch dL/dpix_c)^2
 //   MOM 2 (SH colours, 34 sums): [13, 19) sum dch^2 dL/dpix_c dL/dpix_d (c <= d, row-major),
 //                                [19, 34) sum u_i dch dL/dpix_c (i-major)
-template <bool DUAL, bool OPAC, bool COL1, bool COL2, int Q2, int MOM = 0, int C1 = 3>
-constexpr int bwd_nv() { return MOM == 1 ? 16 : (MOM == 2 ? 34 : 5 + (OPAC ? 1 : 0) + (COL1 ? C1 : 0) + (COL2 ? Q2 : 0)); }
+template <bool DUAL, bool OPAC, bool COL1, bool COL2, int Q2, int MOM = 0, int C1 = 3, bool M2D1 = false>
+constexpr int bwd_nv() {
+    return MOM == 1 ? 16 : (MOM == 2 ? 34 : 5 + (OPAC ? 1 : 0) + (COL1 ? C1 : 0) + (COL2 ? Q2 : 0) + (M2D1 ? 2 : 0));
+}
 __host__ __device__ constexpr int mono_t(int a, int b) {  // monomial index of dx^a dy^b, a + b in {2, 3, 4}
     return a + b == 2 ? 2 - a : (a + b == 3 ? 3 + (3 - a) : 7 + (4 - a));
 }
@@ -240,11 +248,11 @@ constexpr int bwd_waves() {
 // depth/silhouette render: its loss differentiates the depth channel only) -- one colour sum instead of
 // three; the batch shape and the record layout stay those of the C1 = 3 variant (the two missing sums are
 // stored as zeros), so both serve the same launch.
-template <bool DUAL, bool OPAC, bool COL1, bool COL2, int Q2, int MOM, int C1 = 3>
+template <bool DUAL, bool OPAC, bool COL1, bool COL2, int Q2, int MOM, int C1 = 3, bool M2D1 = false>
 struct BwdShape {
-    static constexpr int NV = bwd_nv<DUAL, OPAC, COL1, COL2, Q2, MOM, C1>();
-    static constexpr int NV3 = bwd_nv<DUAL, OPAC, COL1, COL2, Q2, MOM, 3>();
-    static constexpr int BB = bwd_batch<NV3, MOM>(), BS = bwd_slots<NV3, MOM>();
+    static constexpr int NV = bwd_nv<DUAL, OPAC, COL1, COL2, Q2, MOM, C1, M2D1>();
+    static constexpr int NV3 = bwd_nv<DUAL, OPAC, COL1, COL2, Q2, MOM, 3, M2D1>();
+    static constexpr int BB = bwd_batch<NV3, MOM>(), BS = M2D1 ? GSR_BWD_M2D_BS : bwd_slots<NV3, MOM>();
     static constexpr int RS = (NV3 + 1) & ~1;  // record stride (floats)
     static constexpr int LS = BB + 4;          // row-list stride (u32)
     // entry BB is a dummy (opacity 0, never blends) that pads the row lists; its slot BS
@@ -271,7 +279,12 @@ struct BwdPix {
     float dp0, dp1, dp2, dq0, dq1, dq2;
 };
 
-template <bool DUAL, bool OPAC, bool COL1, bool COL2, int Q2, int MOM, int C1 = 3>
+// M2D1 (the mapping form only: DUAL, OPAC, COL1, COL2, Q2 = 1): the first colour set's own share of (hx, hy) as
+// two more sums per pair, from a second accumulator A1 that follows the single-image variant's recurrence
+// operation for operation (A1_0 = bg . dL/dpix, e1 = c . dL/dpix - A1, x1 = e1 Tn, A1 <- fma(alpha, e1, A1)); the
+// pair adds (araw x1) dx and (araw x1) dy, masked like dLa.  Gaussian-splatting densification reads the RGB
+// render's own means2D gradient (scripts/splatam.py:256), which the shared accumulator A does not separate.
+template <bool DUAL, bool OPAC, bool COL1, bool COL2, int Q2, int MOM, int C1 = 3, bool M2D1 = false>
 __device__ __forceinline__ void bwd_tile(const Camera& cam, int tile, const BwdPix& pin,
                                          const uint2* __restrict__ ranges, const PointEntry* __restrict__ point_list,
                                          const float4* __restrict__ rr, const uint32_t* __restrict__ blocksums,
@@ -281,7 +294,8 @@ __device__ __forceinline__ void bwd_tile(const Camera& cam, int tile, const BwdP
     static_assert(!MOM || (!DUAL && OPAC && COL1), "the moment variants form every single-image gradient");
     static_assert(Q2 == 1 || Q2 == 3, "Q2 is 1 or 3 channels");
     static_assert(C1 == 3 || (C1 == 1 && COL1 && !DUAL && !MOM), "one colour sum: single-image colour variants only");
-    using L = BwdShape<DUAL, OPAC, COL1, COL2, Q2, MOM, C1>;
+    static_assert(!M2D1 || (DUAL && OPAC && COL1 && COL2 && Q2 == 1 && !MOM && C1 == 3), "M2D1: the mapping form only");
+    using L = BwdShape<DUAL, OPAC, COL1, COL2, Q2, MOM, C1, M2D1>;
     constexpr int NV = L::NV;
     constexpr int O_C1 = 5 + (OPAC ? 1 : 0);
     constexpr int BB = L::BB, BS = L::BS, RS = L::RS, LS = L::LS;
@@ -344,6 +358,8 @@ __device__ __forceinline__ void bwd_tile(const Camera& cam, int tile, const BwdP
     // A' <- A' + alpha (c . dL/dpix - A') (T_n = T / (1 - alpha)), from A'_0 = bg . dL/dpix: the colour
     // behind the last Gaussian is the background.  Bitwise the plain recurrence when bg = 0.
     float bg_dot = cam.bg[0] * dp0 + cam.bg[1] * dp1 + cam.bg[2] * dp2;
+    [[maybe_unused]] float A1 = 0.f;  // (M2D1) the first colour set's accumulator: its background term alone
+    if constexpr (M2D1) A1 = bg_dot;
     if (DUAL) bg_dot += cam.bg[0] * dq0 + cam.bg[1] * dq1 + cam.bg[2] * dq2;
     const v2f pix = v2f{(float)px, (float)py};
     const v2f dp01 = v2f{dp0, dp1}, dq01 = v2f{dq0, dq1};
@@ -479,6 +495,7 @@ __device__ __forceinline__ void bwd_tile(const Camera& cam, int tile, const BwdP
             // cost 2 VALU + a branch per step; config-4 dual 396 -> 387 us without it)
             // serial part (in list order): T and A, then dL/dalpha and dchannel/dcolor
             float dLa[4], dch[4];
+            [[maybe_unused]] float h1[4];  // (M2D1) araw dL/dalpha of the first colour set alone
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const float4 c = rec(s_c, k);
@@ -503,6 +520,13 @@ __device__ __forceinline__ void bwd_tile(const Camera& cam, int tile, const BwdP
                 const float x = xd.x;
                 dch[k] = xd.y;                          // 0 when masked
                 dLa[k] = (OPAC && !ok[k]) ? 0.f : x;    // (without OPAC: h = araw dLa is 0 when masked)
+                if constexpr (M2D1) {  // the single-image variant's operations, on the first colour set alone
+                    const v2f t1 = v2f{c.x, c.y} * dp01;
+                    const float e1 = __builtin_fmaf(c.z, dp2, t1.x + t1.y) - A1;
+                    const float x1 = e1 * Tn;
+                    h1[k] = araw[k] * (ok[k] ? x1 : 0.f);
+                    A1 = __builtin_fmaf(alpha[k], e1, A1);
+                }
                 T = Tn;  // masked pairs: alpha = 0 and v_rcp_f32(1) == 1 exactly (tools/micro/rcp_one.hip)
                 A = __builtin_fmaf(alpha[k], e, A);     // unchanged when masked
             }
@@ -563,7 +587,17 @@ __device__ __forceinline__ void bwd_tile(const Camera& cam, int tile, const BwdP
             } else {  // wide variants: geometric (+ opacity), then colour sums (register pressure).  G dL/dalpha
                 // rides with the 5 geometric sums: 6 + 6 instead of 5 + 7 sums for mapping is 84 instead of 96 DPP
                 // adds per step (render_bwd 312 -> 303 us at config 4, profiles/r3_split_ab.txt)
-                constexpr int NA = 5 + (OPAC ? 1 : 0), NB = NV - NA;
+                constexpr int NA = 5 + (OPAC ? 1 : 0), NB = NV - NA - (M2D1 ? 2 : 0);
+                if constexpr (M2D1) {  // the pair first, a pass of its own: h1 is dead before the wide passes
+                    float v[4 * 2];
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const v2f m = h1[k] * d[k];
+                        v[2 * k] = m.x;
+                        v[2 * k + 1] = m.y;
+                    }
+                    reduce_store<2>(v, lane, dst + NA + NB, true);
+                }
                 {
                     float v[4 * NA];
 #pragma unroll
@@ -688,6 +722,50 @@ render_bwd_kernel(Camera cam, const uint2* __restrict__ ranges, const PointEntry
         }
     }
     bwd_tile<DUAL, OPAC, COL1, COL2, Q2, MOM>(cam, tile, pin, ranges, point_list, rr, blocksums, inst, guard, smem, dg);
+    dg.end();
+    kclock_end(clk);
+}
+
+// The mapping form with the first colour set's own (hx, hy) sums (bwd_tile's M2D1): a kernel of its own, so that
+// no existing instantiation's name, arguments or code change.  4 waves per SIMD: the mapping variant sits at 94 of
+// the 96 VGPRs that 5 waves allow, and the second accumulator with its four per-pair products spilled there (44 B
+// of scratch per lane with the pair as its own pass, 68 B riding with the colour sums: tools/kernel_resources.py).
+#ifndef GSR_BWD_M2D_WAVES
+#define GSR_BWD_M2D_WAVES 4
+#endif
+__global__ void __launch_bounds__(TILE_PIX, GSR_BWD_M2D_WAVES)
+render_bwd_m2d_kernel(Camera cam, const uint2* __restrict__ ranges, const PointEntry* __restrict__ point_list,
+                      const float4* __restrict__ rr, const uint32_t* __restrict__ blocksums,
+                      const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
+                      const float* __restrict__ dL_dpix, const float* __restrict__ dL_dpix2, float* __restrict__ inst,
+                      BwdGuard guard, unsigned long long* clk) {
+    kclock_begin(clk);
+    RenderDiag dg;
+    dg.begin();
+    if (guard.overflow()) {
+        kclock_end(clk);
+        return;
+    }
+    __shared__ __attribute__((aligned(16))) char smem[BwdShape<true, true, true, true, 1, 0, 3, true>::bytes];
+    // (render_bwd_kernel's own pixel loads, DUAL with Q2 = 1: that kernel's text stays as it is)
+    const int tid = threadIdx.x;
+    const int tile = sched_tile(cam), tx = tile % cam.gx, ty = tile / cam.gx;
+    dg.tile(tile);
+    const int px = tx * TILE_X + tile_px(tid);
+    const int py = ty * TILE_Y + tile_py(tid);
+    const int pid = py * cam.W + px;
+    const int HW = cam.W * cam.H;
+    BwdPix pin{0.f, 0u, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (px < cam.W && py < cam.H) {
+        pin.T_final = final_T[pid];
+        pin.last = n_contrib[pid];
+        pin.dp0 = dL_dpix[pid];
+        pin.dp1 = dL_dpix[HW + pid];
+        pin.dp2 = dL_dpix[2 * HW + pid];
+        pin.dq0 = dL_dpix2[pid];
+    }
+    bwd_tile<true, true, true, true, 1, 0, 3, true>(cam, tile, pin, ranges, point_list, rr, blocksums, inst, guard, smem,
+                                                    dg);
     dg.end();
     kclock_end(clk);
 }
@@ -817,16 +895,33 @@ hipError_t launch_render_bwd(const Camera& cam, const uint2* ranges, const uint6
     return hipGetLastError();
 }
 
+int m2d_record_stride() { return BwdShape<true, true, true, true, 1, 0, 3, true>::RS; }
+static_assert(BwdShape<true, true, true, true, 1, 0, 3, true>::NV == M2D_REC_PAIR + 2 &&
+                  BwdShape<true, true, true, true, 1, 0, 3, true>::RS <= INST_REC_MAX,
+              "the M2D1 record: the mapping variant's ten sums, then the pair");
+
+hipError_t launch_render_bwd_m2d(const Camera& cam, const uint2* ranges, const uint64_t* point_list, GeomPtrs geo,
+                                 const float* final_T, const uint32_t* n_contrib, const float* dL_dpix,
+                                 const float* dL_dpix2, float* inst, BwdGuard guard, hipStream_t s,
+                                 unsigned long long* clk) {
+    hipLaunchKernelGGL(render_bwd_m2d_kernel, dim3(cam.gx * cam.gy), dim3(TILE_PIX), 0, s, cam, ranges, point_list,
+                       geo.rr, geo.blocksums, final_T, n_contrib, dL_dpix, dL_dpix2, inst, guard, clk);
+    return hipGetLastError();
+}
+
 // SHL: per-lane SH chain (g.shs may be set).  Without it (colours precomputed, or SH handled by
 // the staged sh_bwd_kernel) g.shs is NULL at compile time, and the 48-float dsh array and the SH
 // chain drop out of the kernel (mapping variant: 142 -> fewer VGPRs, more waves per SIMD).
 // at most 5 waves per SIMD: at 78-80 VGPRs the kernel would run 6, and the sixth wave measured slower for the
 // mapping variant (1 M anisotropic Gaussians: 65.0 -> 64.0 us capped) and no faster for tracking
 // (profiles/r5z_ab_gauss_bwd_waves.txt)
-template <bool POSE, bool SHL>
+// M2D1 (m1.dmeans2D_c1 set): the records carry the first colour set's own (hx, hy) at m1.o_m1; its means2D
+// gradient -ddel (Q [hx1, hy1]) -- the expression that forms g2[0..1] -- goes to m1.dmeans2D_c1, z as 0.
+template <bool POSE, bool SHL, bool M2D1 = false>
 __device__ __forceinline__ void gauss_bwd_body(Camera cam, GaussIn g, GeomPtrs geo, const int* __restrict__ radii,
                                                const float* __restrict__ inst, RecLayout rec, GradsOut out,
-                                               BwdGuard guard, PoseFuse pf) {
+                                               BwdGuard guard, PoseFuse pf, M2dOut m1 = M2dOut{}) {
+    static_assert(!M2D1 || !POSE, "M2D1: the mapping backward only");
     if constexpr (!SHL) {
         g.shs = nullptr;
         g.M = 0;
@@ -837,6 +932,7 @@ __device__ __forceinline__ void gauss_bwd_body(Camera cam, GaussIn g, GeomPtrs g
     const int nsh = g.shs ? (cam.sh_degree + 1) * (cam.sh_degree + 1) : 0;
     float g2[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float dcol2[3] = {0.f, 0.f, 0.f};
+    [[maybe_unused]] float m2d1[2] = {0.f, 0.f};
     float dmean[3] = {0.f, 0.f, 0.f}, dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, dscale[3] = {0.f, 0.f, 0.f},
           drot[4] = {0.f, 0.f, 0.f, 0.f};
     float dsh[48];
@@ -937,6 +1033,17 @@ __device__ __forceinline__ void gauss_bwd_body(Camera cam, GaussIn g, GeomPtrs g
         const float hx = g2[0], hy = g2[1];
         g2[0] = -(ca * hx + cb * hy) * ddelx;
         g2[1] = -(cc * hy + cb * hx) * ddely;
+        if constexpr (M2D1) {
+            float hx1 = 0.f, hy1 = 0.f;
+#pragma unroll
+            for (int m = 0; m + 1 < INST_REC_MAX; m++)
+                if (m == m1.o_m1) {
+                    hx1 = acc[m];
+                    hy1 = acc[m + 1];
+                }
+            m2d1[0] = -(ca * hx1 + cb * hy1) * ddelx;
+            m2d1[1] = -(cc * hy1 + cb * hx1) * ddely;
+        }
         g2[2] *= -0.5f;
         g2[3] *= -0.5f;
         g2[4] *= -0.5f;
@@ -1028,6 +1135,11 @@ __device__ __forceinline__ void gauss_bwd_body(Camera cam, GaussIn g, GeomPtrs g
         out.dmeans2D[3 * i + 1] = g2[1];
         out.dmeans2D[3 * i + 2] = 0.f;
     }
+    if constexpr (M2D1) {
+        m1.dmeans2D_c1[3 * i] = m2d1[0];
+        m1.dmeans2D_c1[3 * i + 1] = m2d1[1];
+        m1.dmeans2D_c1[3 * i + 2] = 0.f;
+    }
     if (out.dcolors) {
         out.dcolors[3 * i] = g2[6];
         out.dcolors[3 * i + 1] = g2[7];
@@ -1067,6 +1179,15 @@ gauss_bwd_kernel(Camera cam, GaussIn g, GeomPtrs geo, const int* __restrict__ ra
     if constexpr (CLK) kclock_end(clk);
 }
 
+template <bool SHL, bool CLK>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 5)))
+gauss_bwd_m2d_kernel(Camera cam, GaussIn g, GeomPtrs geo, const int* __restrict__ radii, const float* __restrict__ inst,
+                     RecLayout rec, GradsOut out, M2dOut m1, BwdGuard guard, unsigned long long* clk) {
+    if constexpr (CLK) kclock_begin(clk);
+    gauss_bwd_body<false, SHL, true>(cam, g, geo, radii, inst, rec, out, guard, PoseFuse{}, m1);
+    if constexpr (CLK) kclock_end(clk);
+}
+
 // arrival counters, workgroup partials, the 16 group sums
 int pose_fuse_scratch_floats(int P) { return POSE_PARTS * ((P + 255) / 256) + ARRIVE_GROUPED_WORDS + 16 * POSE_PARTS; }
 
@@ -1081,6 +1202,17 @@ hipError_t launch_gauss_bwd(const Camera& cam, const GaussIn& g, GeomPtrs geo, c
                          : (shl ? gauss_bwd_kernel<false, true, false> : gauss_bwd_kernel<false, false, false>));
     hipLaunchKernelGGL(k, dim3((g.P + 255) / 256), dim3(256), 0, s, cam, g, geo, radii, inst, rec, out, guard,
                        pose ? *pose : PoseFuse{}, clk);
+    return hipGetLastError();
+}
+
+hipError_t launch_gauss_bwd_m2d(const Camera& cam, const GaussIn& g, GeomPtrs geo, const int* radii, const float* inst,
+                                RecLayout rec, const GradsOut& out, M2dOut m1, BwdGuard guard, hipStream_t s,
+                                unsigned long long* clk) {
+    if (g.P == 0) return hipSuccess;
+    const bool shl = g.shs != nullptr;
+    auto k = clk ? (shl ? gauss_bwd_m2d_kernel<true, true> : gauss_bwd_m2d_kernel<false, true>)
+                 : (shl ? gauss_bwd_m2d_kernel<true, false> : gauss_bwd_m2d_kernel<false, false>);
+    hipLaunchKernelGGL(k, dim3((g.P + 255) / 256), dim3(256), 0, s, cam, g, geo, radii, inst, rec, out, m1, guard, clk);
     return hipGetLastError();
 }
 

@@ -609,6 +609,7 @@ struct BwdCall {
     const PoseFuse* pose = nullptr;
     const ShAdam* sh_adam = nullptr;
     const float* pre_inst = nullptr;
+    float* dmeans2D_c1 = nullptr;  // gsr_backward_dual_m2d: the first colour set's own means2D gradient
 };
 
 // the group every backward entry passes: inputs, radii and the forward's state ...
@@ -755,7 +756,17 @@ struct Backward {
             pose ? (NEED_COLORS2 | NEED_DL2_CH0_ONLY)
                  : (out.dopacity ? NEED_OPACITY : 0u) | ((out.dcolors || g.shs) ? NEED_COLORS : 0u) |
                        (c.dcolors2 ? NEED_COLORS2 : 0u) | (c.dl2_channels == 1 ? NEED_DL2_CH0_ONLY : 0u);
-        const RecLayout rec = bwd_rec_layout(need, c.colors2 != nullptr);
+        RecLayout rec = bwd_rec_layout(need, c.colors2 != nullptr);
+        // gsr_backward_dual_m2d: the mapping variant's record with the first colour set's (hx, hy) behind it
+        constexpr unsigned kMapNeed = NEED_OPACITY | NEED_COLORS | NEED_COLORS2 | NEED_DL2_CH0_ONLY;
+        M2dOut m1;
+        if (c.dmeans2D_c1) {
+            if (need != kMapNeed || !c.colors2 || pose || c.pre_inst || rec.stride != M2D_REC_PAIR)
+                return fail(GSR_ERR_INVALID_ARG, "backward_dual_m2d: the mapping form only");
+            m1.dmeans2D_c1 = c.dmeans2D_c1;
+            m1.o_m1 = M2D_REC_PAIR;
+            rec.stride = m2d_record_stride();
+        }
         // staged SH backward: gauss_bwd leaves dL/dcolor in a scratch array, sh_bwd turns it into dsh and the
         // view-direction term of dL/dmeans3D (gsr_sh.hip)
         const bool shs_staged = sh_staged(cam, g);
@@ -783,10 +794,12 @@ struct Backward {
             if (!c.binning_buffer) return fail(GSR_ERR_INVALID_ARG, "missing binning buffer");
             inst = (float*)scratch;
             StageTimer t(GSR_STAGE_RENDER_BWD, R, stream, true);
-            if ((e = launch_render_bwd(cam, img.ranges, point_list, geo, img.final_T, img.n_contrib, c.dL_dout_color,
-                                       c.colors2, c.dL_dout_color2, need, inst, guard, stream, t.kclock())) !=
-                hipSuccess)
-                return hip_fail(e, "render backward");
+            e = m1.dmeans2D_c1
+                    ? launch_render_bwd_m2d(cam, img.ranges, point_list, geo, img.final_T, img.n_contrib,
+                                            c.dL_dout_color, c.dL_dout_color2, inst, guard, stream, t.kclock())
+                    : launch_render_bwd(cam, img.ranges, point_list, geo, img.final_T, img.n_contrib, c.dL_dout_color,
+                                        c.colors2, c.dL_dout_color2, need, inst, guard, stream, t.kclock());
+            if (e != hipSuccess) return hip_fail(e, "render backward");
         }
         out.dcolors2 = c.dcolors2;
         // (device-clock mode: gauss_bwd_kernel stamps itself; a staged sh_bwd after it is not timed)
@@ -804,9 +817,11 @@ struct Backward {
             pc = *pose;
             pc.guard = geo.counters;
         }
-        if ((e = launch_gauss_bwd(cam, gc, geo, c.radii, inst, rec, oc, guard, stream, pose ? &pc : nullptr,
-                                  t.kclock())) != hipSuccess)
-            return hip_fail(e, "gaussian backward");
+        e = m1.dmeans2D_c1
+                ? launch_gauss_bwd_m2d(cam, gc, geo, c.radii, inst, rec, oc, m1, guard, stream, t.kclock())
+                : launch_gauss_bwd(cam, gc, geo, c.radii, inst, rec, oc, guard, stream, pose ? &pc : nullptr,
+                                   t.kclock());
+        if (e != hipSuccess) return hip_fail(e, "gaussian backward");
         // the colour step guards on this call's own forward counters (not a sticky status row: an
         // overflow in an earlier replay must not skip the steps of later valid iterations)
         ShAdam sa = c.sh_adam ? *c.sh_adam : ShAdam{};
@@ -1208,6 +1223,26 @@ int gsr_backward_dual(const gsr_settings* settings, const gsr_gaussians* gaussia
     BwdCall c = bwd_call(settings, gaussians, radii, num_rendered, geom_buffer, binning_buffer, image_buffer);
     c.colors2 = colors2; c.dL_dout_color = dL_dout_color; c.dL_dout_color2 = dL_dout_color2;
     c.grads = grads; c.dcolors2 = dcolors2; c.dl2_channels = dl2_channels;
+    return backward_impl(on(c, alloc, alloc_ctx, stream));
+}
+
+int gsr_backward_dual_m2d(const gsr_settings* settings, const gsr_gaussians* gaussians, const int* radii,
+                          const float* colors2, const float* dL_dout_color, const float* dL_dout_color2,
+                          int num_rendered, const void* geom_buffer, const void* binning_buffer,
+                          const void* image_buffer, const gsr_grads* grads, float* dcolors2, int dl2_channels,
+                          float* dmeans2D_color1, gsr_alloc_fn alloc, void* alloc_ctx, void* stream) {
+    // the sibling's own checks come before the shared ones (like check_terms for the _terms entries)
+    if (!dmeans2D_color1) return fail(GSR_ERR_INVALID_ARG, "backward_dual_m2d: dmeans2D_color1 must not be NULL");
+    if ((uintptr_t)dmeans2D_color1 % 4 != 0)
+        return fail(GSR_ERR_INVALID_ARG, "backward_dual_m2d: dmeans2D_color1 must be 4-byte aligned");
+    if (!colors2) return fail(GSR_ERR_INVALID_ARG, "colors2 required");
+    if (dl2_channels != 1) return fail(GSR_ERR_INVALID_ARG, "backward_dual_m2d: dl2_channels must be 1");
+    if (!grads || !grads->dopacity || !dcolors2 || (!grads->dcolors && !(gaussians && gaussians->shs)))
+        return fail(GSR_ERR_INVALID_ARG, "backward_dual_m2d: the mapping form only (dopacity, dcolors2 and dcolors "
+                                         "or SH colours)");
+    BwdCall c = bwd_call(settings, gaussians, radii, num_rendered, geom_buffer, binning_buffer, image_buffer);
+    c.colors2 = colors2; c.dL_dout_color = dL_dout_color; c.dL_dout_color2 = dL_dout_color2;
+    c.grads = grads; c.dcolors2 = dcolors2; c.dl2_channels = dl2_channels; c.dmeans2D_c1 = dmeans2D_color1;
     return backward_impl(on(c, alloc, alloc_ctx, stream));
 }
 

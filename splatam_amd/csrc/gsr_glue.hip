@@ -189,6 +189,33 @@ fisher_accumulate_kernel(int P, const float* __restrict__ dm, const float* __res
     h.w = h.w + dop[i] * s;
     reinterpret_cast<float4*>(H)[i] = h;
 }
+// Densification statistics of one mapping iteration (slam_external.py:100-104 with splatam.py:349): one lane
+// per Gaussian, rows with radius <= 0 untouched.  The norm is sqrtf(gx^2 + gy^2) with the operands scaled by an
+// exact power of two first, so a denormal gradient's squares do not flush to zero: the same bits wherever the
+// plain expression neither underflows nor overflows.
+__global__ void __launch_bounds__(GLUE_BLOCK)
+accumulate_mean2d_kernel(int P, const int* __restrict__ radii, const float* __restrict__ g, float* __restrict__ accum,
+                         float* __restrict__ denom, float* __restrict__ maxr) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    const int r = radii[i];
+    if (r <= 0) return;
+    const float gx = g[3 * i], gy = g[3 * i + 1];
+    const float m = fmaxf(fabsf(gx), fabsf(gy));
+    float n;
+    if (m > 0.f && m <= 3.402823466e38f) {
+        int e;
+        (void)frexpf(m, &e);  // m = f 2^e, f in [0.5, 1)
+        const float sx = ldexpf(gx, -e), sy = ldexpf(gy, -e);
+        n = ldexpf(sqrtf(sx * sx + sy * sy), e);
+    } else {
+        n = sqrtf(gx * gx + gy * gy);  // 0, inf or NaN
+    }
+    accum[i] = accum[i] + n;
+    denom[i] = denom[i] + 1.f;
+    maxr[i] = fmaxf(maxr[i], (float)r);
+}
 
 int blocks_for(int n) { return n <= 0 ? 1 : std::min(GLUE_MAX_BLOCKS, (n + GLUE_BLOCK - 1) / GLUE_BLOCK); }
 // the pose reduction's last workgroup reads 16 partials per workgroup: fewer, fuller workgroups
@@ -343,6 +370,18 @@ int gsr_points_to_camera(int P, const float* means, const float* w2c, float* pts
                        (hipStream_t)stream, P, means, w2c, pts);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? GSR_OK : hip_fail(e, "points_to_camera");
+}
+
+int gsr_accumulate_mean2d(int P, const int* radii, const float* dmeans2D, float* accum, float* denom,
+                          float* max_2D_radius, void* stream) {
+    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "accumulate_mean2d: bad size");
+    if (P == 0) return GSR_OK;
+    if (!radii || !dmeans2D || !accum || !denom || !max_2D_radius)
+        return fail(GSR_ERR_INVALID_ARG, "accumulate_mean2d: null pointer");
+    hipLaunchKernelGGL(accumulate_mean2d_kernel, dim3((P + GLUE_BLOCK - 1) / GLUE_BLOCK), dim3(GLUE_BLOCK), 0,
+                       (hipStream_t)stream, P, radii, dmeans2D, accum, denom, max_2D_radius);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GSR_OK : hip_fail(e, "accumulate_mean2d");
 }
 
 int gsr_fisher_accumulate(int P, const float* dmeans3D, const float* dopacity, const float* weight, float* H,

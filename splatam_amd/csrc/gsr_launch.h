@@ -103,6 +103,24 @@ struct GradsOut {
     float* drot;
     float* dcolors2;  // second colour set of a dual render (nullptr otherwise)
 };
+// gsr_backward_dual_m2d: the mapping form's render backward with the first colour set's own (hx, hy) sums
+// (bwd_tile's M2D1) and the per-Gaussian backward that turns them into that set's means2D gradient.  The
+// record is the mapping variant's ten sums, then the pair at M2D_REC_PAIR: 12 floats, the stated maximum.
+// M2dOut is a record of its own, not a field of RecLayout / GradsOut: those are by-value arguments of every
+// gauss_bwd_kernel instantiation, whose argument layout (and device code) must not move.
+constexpr int M2D_REC_PAIR = 10;
+struct M2dOut {
+    float* dmeans2D_c1 = nullptr;  // [P,3]: (x, y) in NDC units like dmeans2D, z written as 0
+    int o_m1 = -1;                 // record offset of the pair, -1 when absent
+};
+int m2d_record_stride();
+hipError_t launch_render_bwd_m2d(const Camera& cam, const uint2* ranges, const uint64_t* point_list, GeomPtrs geo,
+                                 const float* final_T, const uint32_t* n_contrib, const float* dL_dpix,
+                                 const float* dL_dpix2, float* inst, BwdGuard guard, hipStream_t s,
+                                 unsigned long long* clk = nullptr);
+hipError_t launch_gauss_bwd_m2d(const Camera& cam, const GaussIn& g, GeomPtrs geo, const int* radii, const float* inst,
+                                RecLayout rec, const GradsOut& out, M2dOut m1, BwdGuard guard, hipStream_t s,
+                                unsigned long long* clk = nullptr);
 // Tracking (gsr_track_backward_dual): the pose gradient -- and the pose Adam step -- fused into
 // gauss_bwd, whose per-Gaussian dL/dmeans_cam, dL/d[z,1,z^2] and (anisotropic) dL/drotation
 // never leave registers.  Same maths as track_transform_bwd_kernel (gsr_glue.hip).

@@ -421,6 +421,30 @@ def map_prune(params: dict, alive: torch.Tensor, opac_thr: float, big_thr: float
     check_rc(rc, "map_prune")
 
 
+def accumulate_mean2d(variables: dict, radius: torch.Tensor, means2D_grad: torch.Tensor):
+    """gsr_accumulate_mean2d: Gaussian-splatting densification's per-iteration statistics
+    (accumulate_mean2d_gradient, slam_external.py:100-104, with splatam.py:349-351) in one launch, in place and
+    without the reference's boolean index and its host read: for radius > 0, means2D_gradient_accum += the norm
+    of means2D_grad[:, :2], denom += 1, max_2D_radius = max(max_2D_radius, radius).  means2D_grad [P,3]: the RGB
+    render's own means2D gradient (rasterize_gaussians_dual(means2D_grad_color1=True)).  variables["seen"] is
+    set to radius > 0 like the reference's get_loss does."""
+    acc, den, mx = (_f32c(variables[k], k) for k in ("means2D_gradient_accum", "denom", "max_2D_radius"))
+    g = _f32c(means2D_grad, "means2D_grad")
+    P = g.shape[0]
+    if g.dim() != 2 or g.shape[1] != 3 or radius.dtype != torch.int32 or radius.device != g.device or \
+            not radius.is_contiguous() or any(t.numel() != P or t.device != g.device for t in (radius, acc, den, mx)):
+        raise RuntimeError("accumulate_mean2d: means2D_grad [P,3] float32, radius [P] int32 and the three statistics "
+                           "[P] float32, contiguous on one device")
+    for k, t in (("means2D_gradient_accum", acc), ("denom", den), ("max_2D_radius", mx)):
+        if t.data_ptr() != variables[k].data_ptr():
+            raise RuntimeError(f"accumulate_mean2d: variables[{k!r}] is updated in place and must be contiguous")
+    rc = lib.gsr_accumulate_mean2d(P, radius.data_ptr(), g.data_ptr(), acc.data_ptr(), den.data_ptr(), mx.data_ptr(),
+                                   _stream(g))
+    check_rc(rc, "accumulate_mean2d")
+    variables["seen"] = radius > 0
+    return variables
+
+
 def map_transform(params: dict, time_idx: int, w2c: torch.Tensor, color_key: str = "rgb_colors",
                   adam: MapAdam | None = None, defer: list | None = None):
     """transform_to_frame(params, t, gaussians_grad=True, camera_grad=False) (slam_helpers.py:252-304)

@@ -85,7 +85,8 @@ class _RasterizeGaussians(torch.autograd.Function):
 
 def rasterize_gaussians_dual(means3D, means2D, sh, colors_precomp, colors2, opacities, scales, rotations,
                              cov3Ds_precomp, raster_settings, capacity=0, status=None, grad2_channels=3,
-                             means2D_grad_sum=False, sh_adam=None, guard_sink=None, alive=None, xform=None):
+                             means2D_grad_sum=False, sh_adam=None, guard_sink=None, alive=None, xform=None,
+                             means2D_grad_color1=False):
     """Two GaussianRasterizer calls on identical geometry fused into one
     rasterization: SplaTAM renders RGB and the [z, 1, z^2]
     depth/silhouette image from the same means / scales / rotations / opacities
@@ -96,7 +97,9 @@ def rasterize_gaussians_dual(means3D, means2D, sh, colors_precomp, colors2, opac
     gradient of the RGB render's own means2D (scripts/splatam.py:256), which one rasterization of
     both images does not separate, so means2D receives no gradient unless means2D_grad_sum=True
     asks for the sum over both images; callers that need the RGB-only statistic render the two
-    images with two GaussianRasterizer calls.
+    images with two GaussianRasterizer calls, or pass means2D_grad_color1=True: means2D then receives the first
+    colour set's own gradient (gsr_backward_dual_m2d; the mapping form only: grad2_channels=1, every Gaussian
+    gradient wanted, no sh_adam).  The two means2D keywords exclude each other (ValueError).
     capacity > 0: synchronisation-free static mode (gsr_forward_dual_static),
     for HIP-graph capture; check `status` (device int32[4]) afterwards.
     grad2_channels=1: the caller's loss reads only channel 0 of color2 (SplaTAM
@@ -110,6 +113,11 @@ def rasterize_gaussians_dual(means3D, means2D, sh, colors_precomp, colors2, opac
     xform: the mapping transform deferred into this forward (glue.map_transform(defer=...)): preprocess forms
     means3D / rotations / colors2 / opacities / scales from the world-frame map and writes them
     (gsr_forward_dual_static_xf; static mode, precomputed colours)."""
+    if means2D_grad_sum and means2D_grad_color1:
+        raise ValueError("rasterize_gaussians_dual: means2D_grad_sum and means2D_grad_color1 exclude each other")
+    if means2D_grad_color1 and (sh_adam is not None or grad2_channels != 1):
+        raise ValueError("rasterize_gaussians_dual: means2D_grad_color1 is the mapping form's (grad2_channels=1, "
+                         "no sh_adam)")
     empty = torch.Tensor([])
     return _RasterizeGaussiansDual.apply(means3D, means2D, empty if sh is None else sh,
                                          empty if colors_precomp is None else colors_precomp, colors2, opacities,
@@ -117,14 +125,14 @@ def rasterize_gaussians_dual(means3D, means2D, sh, colors_precomp, colors2, opac
                                          empty if rotations is None else rotations,
                                          empty if cov3Ds_precomp is None else cov3Ds_precomp, raster_settings,
                                          capacity, status, grad2_channels, bool(means2D_grad_sum), sh_adam,
-                                         guard_sink, alive, xform)
+                                         guard_sink, alive, xform, bool(means2D_grad_color1))
 
 
 class _RasterizeGaussiansDual(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, colors2, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings, capacity, status, grad2_channels, means2D_grad_sum, sh_adam=None, guard_sink=None,
-                alive=None, xform=None):
+                alive=None, xform=None, means2D_grad_color1=False):
         s = raster_settings
         num_rendered, color, color2, radii, geomBuffer, binningBuffer, imgBuffer, depth = _C.rasterize_gaussians_dual(
             s.bg, means3D, colors_precomp, colors2, opacities, scales, rotations, s.scale_modifier, cov3Ds_precomp,
@@ -146,6 +154,7 @@ class _RasterizeGaussiansDual(torch.autograd.Function):
         ctx.num_rendered = num_rendered
         ctx.grad2_channels = grad2_channels
         ctx.means2D_grad_sum = means2D_grad_sum
+        ctx.means2D_grad_color1 = means2D_grad_color1
         ctx.sh_adam = sh_adam
         ctx.save_for_backward(colors_precomp, colors2, means3D, scales, rotations, cov3Ds_precomp, radii, sh,
                               geomBuffer, binningBuffer, imgBuffer)
@@ -163,7 +172,8 @@ class _RasterizeGaussiansDual(torch.autograd.Function):
         if grad_color2 is None:
             grad_color2 = torch.zeros(3, s.image_height, s.image_width, device=means3D.device)
         n = ctx.needs_input_grad  # (means3D, means2D, sh, colors_precomp, colors2, opacities, scales, rotations, cov3D)
-        needs = (n[1] and ctx.means2D_grad_sum, n[3], n[4], n[5], n[0], n[8], n[2], n[6], n[7])
+        c1 = n[1] and ctx.means2D_grad_color1
+        needs = (n[1] and (ctx.means2D_grad_sum or c1), n[3], n[4], n[5], n[0], n[8], n[2], n[6], n[7])
         sa = None
         if ctx.sh_adam is not None:  # the colour group's upcoming step (the transform backward counts it)
             sa = ctx.sh_adam.struct()
@@ -172,11 +182,12 @@ class _RasterizeGaussiansDual(torch.autograd.Function):
             s.bg, means3D, radii, colors_precomp, colors2, scales, rotations, s.scale_modifier, cov3Ds_precomp,
             s.viewmatrix, s.projmatrix, s.tanfovx, s.tanfovy, grad_color, grad_color2, sh, s.sh_degree, s.campos,
             geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, needs=needs,
-            dl2_channels=ctx.grad2_channels if grad_color2 is not None else 3, sh_adam=sa)
+            dl2_channels=ctx.grad2_channels if grad_color2 is not None else 3, sh_adam=sa,
+            **({"means2D_color1": True} if c1 else {}))
         if not n[0]:
             g_m3 = None
         return g_m3, g_m2, g_sh, g_col, g_col2, g_op, g_sc, g_rot, g_cov, None, None, None, None, None, None, None, None, \
-            None
+            None, None
 
 
 class GaussianRasterizer(nn.Module):

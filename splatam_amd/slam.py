@@ -476,6 +476,62 @@ def map_frame_literal(params, variables, keyframes, num_iters, cfg: MappingConfi
     return optimizer
 
 
+def fused_densify_eligible(params, curr_data, cfg: MappingConfig) -> bool:
+    """fused_mapping_eligible for the configurations with Gaussian-splatting densification
+    (configs/*/post_splatam_opt.py, configs/*/gaussian_splatting.py): the same conditions with
+    use_gaussian_splatting_densification set.  The dual render backward separates the RGB render's own means2D
+    gradient (rasterize_gaussians_dual(means2D_grad_color1=True)), so map_frame_fused runs them."""
+    from dataclasses import replace
+    return (cfg.use_gaussian_splatting_densification and
+            fused_mapping_eligible(params, curr_data, replace(cfg, use_gaussian_splatting_densification=False)))
+
+
+def map_frame_fused(params, variables, keyframes, num_iters, cfg: MappingConfig = MappingConfig(), optimizer=None,
+                    rng=None, losses_out=None):
+    """map_frame_literal's fused counterpart for the densification configurations (fused_densify_eligible): per
+    iteration glue.map_transform, ONE dual rasterization whose backward hands means2D the RGB render's own
+    gradient, glue.mapping_loss, backward, glue.accumulate_mean2d (the statistics in one launch, no host read),
+    then surgery.prune_gaussians / surgery.densify(accumulate=False) on their schedules and the glue.FusedAdam
+    step.  The surgery is plain torch: it runs every densify_every iterations and changes P.  Keyframes are drawn
+    from `rng` exactly as the literal loop draws them; `params` holds nn.Parameters (as_parameters) and is updated
+    in place (entries replaced when P changes).  Returns the optimizer."""
+    import numpy as np
+    from . import surgery
+    from .glue import accumulate_mean2d, map_transform, mapping_loss
+    rng = np.random if rng is None else rng
+    if not keyframes or not fused_densify_eligible(params, keyframes[0], cfg):
+        raise RuntimeError("map_frame_fused: the configuration is not fused_densify_eligible (map_frame_literal "
+                           "runs it)")
+    if optimizer is None:
+        optimizer = mapping_optimizer(params, cfg, fused=True)
+    key = color_key(params)
+    for it in range(num_iters):
+        kf = keyframes[int(rng.randint(0, len(keyframes)))]
+        means, rots, dcol, opac, scales, col = map_transform(params, kf["id"], kf["w2c"], key)
+        means2D = torch.zeros(means.shape[0], 3, device=means.device, requires_grad=True)
+        sh, colors = (col, None) if key == "shs" else (None, col)
+        im, depth_sil, radius, _ = rasterize_gaussians_dual(means, means2D, sh, colors, dcol, opac, scales, rots, None,
+                                                            kf["cam"], grad2_channels=1, means2D_grad_color1=True)
+        loss = mapping_loss(im, depth_sil, kf["im"], kf["depth"], cfg.w_im, cfg.w_depth)
+        loss.backward()
+        with torch.no_grad():
+            if it <= cfg.densify_dict["stop_after"]:  # (densify accumulates only up to stop_after)
+                accumulate_mean2d(variables, radius, means2D.grad)
+            else:  # splatam.py:349-351 alone
+                variables["seen"] = radius > 0
+                variables["max_2D_radius"] = torch.where(variables["seen"],
+                                                         torch.max(radius.float(), variables["max_2D_radius"]),
+                                                         variables["max_2D_radius"])
+            if cfg.prune_gaussians:
+                surgery.prune_gaussians(params, variables, optimizer, it, cfg.pruning_dict)
+            surgery.densify(params, variables, optimizer, it, cfg.densify_dict, accumulate=False)
+            optimizer.step()
+            optimizer.zero_grad(set_to_none=True)
+        if losses_out is not None:
+            losses_out.append(loss.detach())
+    return optimizer
+
+
 def init_mapping_params(scene: Scene, num_frames: int, device, pose_noise=(0.5, 0.01), seed=0):
     """Mapping parameter dict: init_tracking_params plus anisotropic log_scales [P,3] when the scene
     is anisotropic, and SH colours `shs` [P,M,3] when it carries them (config 4)."""

@@ -98,12 +98,15 @@ def accumulate_mean2d_gradient(variables):
     return variables
 
 
-def densify(params, variables, optimizer, iter, densify_dict):
+def densify(params, variables, optimizer, iter, densify_dict, accumulate=True):
     """slam_external.py:191-243 (Gaussian-Splatting-style clone / split / prune).  The split samples come
-    from torch.normal on the current CUDA generator, like the reference's."""
+    from torch.normal on the current CUDA generator, like the reference's.  accumulate=False: the caller has
+    added this iteration's statistics already (glue.accumulate_mean2d), so accumulate_mean2d_gradient is not
+    called here; the caller then accumulates only while iter <= stop_after, as this function does."""
     from .slam import build_rotation
     if iter <= densify_dict["stop_after"]:
-        variables = accumulate_mean2d_gradient(variables)
+        if accumulate:
+            variables = accumulate_mean2d_gradient(variables)
         grad_thresh = densify_dict["grad_thresh"]
         if iter >= densify_dict["start_after"] and iter % densify_dict["densify_every"] == 0:
             grads = variables["means2D_gradient_accum"] / variables["denom"]

@@ -2,8 +2,13 @@
 
 Compiles every translation unit of build.SOURCES from the working tree and from git revision REV with the
 library's own flags plus --cuda-device-only -S, drops the lines naming the per-compilation __hip_cuid_ symbol,
-and compares the two texts. Prints per file `identical` or the functions whose bodies differ; exits non-zero on
-any difference. Needs hipcc, no GPU.
+and compares the two texts function by function: a function's body and, for a kernel, its .amdhsa_kernel
+descriptor block (registers, LDS, scratch, kernarg size).  Labels carry the function's index in its file
+(.LBB<i>_<n>, .Lfunc_end<i>, `BB<i>_<n>` in the loop comments), which moves when a function is added ahead of it, so the index is dropped before
+comparing.  Prints per file `identical` or the functions whose text differs, and the functions only one side has
+(`added` / `removed`); exits non-zero when a function both sides have differs or one was removed.  With functions
+added, the text outside any function (the metadata listing every kernel) differs by construction and is not
+compared; without, it is.  Needs hipcc, no GPU.
 """
 import os
 import re
@@ -25,15 +30,20 @@ def device_asm(src, csrc, include, out):
     return [ln for ln in open(out).read().splitlines() if "__hip_cuid_" not in ln]
 
 
+_LABEL = re.compile(r"(\.LBB|\.Lfunc_end|\.Lfunc_begin|\.LJTI|\.LCPI|\bBB)\d+(?=_\d|\b)")
+
+
 def functions(lines):
-    """{function name: its lines} (a body runs from its .type directive to .Lfunc_end); the rest under ''."""
+    """{function name: its lines} (a body runs from its .type directive to .Lfunc_end, plus a kernel's
+    .amdhsa_kernel block), function indices dropped from the labels; the rest under ''."""
     out, cur = {"": []}, ""
     for ln in lines:
-        m = re.match(r"\s*\.type\s+([^,\s]+),@function", ln)
+        m = re.match(r"\s*\.type\s+([^,\s]+),@function", ln) or re.match(r"\s*\.amdhsa_kernel\s+(\S+)", ln)
         if m:
             cur = m.group(1)
-        out.setdefault(cur, []).append(ln)
-        if ln.startswith(".Lfunc_end"):
+        # (the label's width sets the padding ahead of its comment: one space)
+        out.setdefault(cur, []).append(re.sub(r"\s+;", " ;", _LABEL.sub(r"\1", ln)) if cur else ln)
+        if ln.startswith(".Lfunc_end") or ln.strip() == ".end_amdhsa_kernel":
             cur = ""
     return out
 
@@ -54,9 +64,15 @@ def main():
     bad = 0
     for src in build.SOURCES:
         old, new = functions(asm[src, "old"]), functions(asm[src, "new"])
-        diff = sorted(f or "(outside any function)" for f in old.keys() | new.keys() if old.get(f) != new.get(f))
-        bad += bool(diff)
-        print(f"{src}: " + ("differs in " + ", ".join(diff) if diff else "identical"))
+        added, removed = sorted(new.keys() - old.keys()), sorted(old.keys() - new.keys())
+        both = [f for f in old.keys() & new.keys() if f or not (added or removed)]
+        diff = sorted(f or "(outside any function)" for f in both if old[f] != new[f])
+        bad += bool(diff or removed)
+        text = "differs in " + ", ".join(diff) if diff else f"identical ({len(both)} functions)"
+        for what, names in (("added", added), ("removed", removed)):
+            if names:
+                text += f"; {what}: " + ", ".join(names)
+        print(f"{src}: {text}")
     return 1 if bad else 0
 
 
