@@ -28,12 +28,20 @@
 // Deliberate difference from the vendored kernel (documented in DESIGN.md):
 // SH gradients follow upstream (every coefficient, DC included, no pointer
 // offset), as in the power-1 path.
+//
+// power == 2 takes a second route, through second moments (launch_render_bwd_moments /
+// launch_gauss_bwd_moments at the end of this file): the power-1 tile backward itself (render_bwd_kernel,
+// gsr_render_bwd.h) in its two MOM forms, which this file instantiates, sums each pair's second moments
+// (gsr_moments.h), and gauss_bwd_mom_kernel applies the chain's quadratic forms once per Gaussian.
 #include <cstdlib>
+#include <utility>
 
 #include "gsr_chain.h"
 #include "gsr_launch.h"
 #include "gsr_layout.h"
 #include "gsr_math.h"
+#include "gsr_moments.h"
+#include "gsr_render_bwd.h"
 #include "gsr_wave.h"
 
 namespace gsr {
@@ -730,6 +738,193 @@ hipError_t launch_gauss_bwd_power(const Camera& cam, const GaussIn& g, GeomPtrs 
         case 16: hipLaunchKernelGGL(gauss_bwd_power_kernel<16>, grid, block, 0, s, g, geo, radii, r, out, guard); break;
         default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------ backward_power == 2 --
+// renderCUDAFused (backward.cu:850-1140) squares every per-pair output before summing it.  Every
+// output of a pair is linear in the pair's base values b = (u, G dL/dalpha, dch dL/dpix) with a
+// per-Gaussian coefficient row n (the chain, the conic and the NDC factor folded in), so
+//   sum_p (n . b_p)^2 = n (sum_p b_p b_p^T) n^T:
+// render_bwd forms the second moments sum_p b_p b_p^T (MOM layout, 16 or 34 sums per instance),
+// and this kernel applies the quadratic forms once per Gaussian, in double.
+hipError_t launch_render_bwd_moments(const Camera& cam, const uint2* ranges, const uint64_t* point_list, GeomPtrs geo,
+                                     const float* final_T, const uint32_t* n_contrib, const float* dL_dpix, bool sh,
+                                     float* inst, BwdGuard guard, hipStream_t s) {
+    auto k = sh ? render_bwd_of<MomVariant<2>>() : render_bwd_of<MomVariant<1>>();
+    hipLaunchKernelGGL(k, dim3(cam.gx * cam.gy), dim3(TILE_PIX), 0, s, cam, ranges, point_list, geo.rr, geo.blocksums,
+                       final_T, n_contrib, dL_dpix, nullptr, inst, guard, nullptr);
+    return hipGetLastError();
+}
+int moments_record_floats(bool sh) { return mom_nv(sh ? 2 : 1); }
+
+template <int MOM>
+__global__ void __launch_bounds__(256)
+gauss_bwd_mom_kernel(Camera cam, GaussIn g, GeomPtrs geo, const int* __restrict__ radii,
+                     const float* __restrict__ inst, GradsOut out, BwdGuard guard) {
+    constexpr int NV = mom_nv(MOM), RS = BwdShape<MomVariant<MOM>>::RS;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g.P) return;
+    const int nsh = g.shs ? (cam.sh_degree + 1) * (cam.sh_degree + 1) : 0;
+    float S[NV];
+#pragma unroll
+    for (int q = 0; q < NV; q++) S[q] = 0.f;
+    const bool live = radii[i] > 0 && !guard.overflow();
+    if (live) {  // fixed-order sum of the Gaussian's instance records (deterministic)
+        const uint32_t off = geo.offsets[i], cnt = geo.tiles[i];
+        const uint32_t tl = reinterpret_cast<const uint32_t*>(geo.bin)[4 * (size_t)i + 3];  // (Camera::cull)
+        for (uint32_t e = 0; e < cnt; e++) {
+            if (!tile_live(tl, e)) continue;
+            const float2* r = reinterpret_cast<const float2*>(inst + (size_t)RS * (off + e));
+            float2 v[RS / 2];
+#pragma unroll
+            for (int m = 0; m < RS / 2; m++) v[m] = r[m];
+#pragma unroll
+            for (int m = 0; m < NV / 2; m++) {
+                S[2 * m] += v[m].x;
+                S[2 * m + 1] += v[m].y;
+            }
+            if (NV % 2) S[NV - 1] += v[NV / 2].x;
+        }
+    }
+    float Sm[9][9];
+    mom_matrix<MOM>(S, Sm, std::make_integer_sequence<int, 81>{});
+    float o_m2[2] = {0.f, 0.f}, o_mean[3] = {0.f, 0.f, 0.f}, o_cov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
+          o_scale[3] = {0.f, 0.f, 0.f}, o_rot[4] = {0.f, 0.f, 0.f, 0.f}, ysq[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) ysq[k] = 0.f;
+    unsigned clamped = 0u;
+    // sum_ab n_a n_b Sm[a][b] over the geometric terms a, b in [A0, 5) and, with nw, the masked colours
+    // (double: the terms of a quadratic form may cancel)
+    auto qform = [&](const float (&n)[5], const float* nw, int A0) -> float {
+        double acc = 0.0;
+#pragma unroll
+        for (int a = 0; a < 5; a++)
+#pragma unroll
+            for (int c = 0; c < 5; c++)
+                if (a >= A0 && c >= A0) acc += (double)n[a] * (double)n[c] * (double)Sm[a][c];
+        if (MOM == 2 && nw) {
+#pragma unroll
+            for (int a = 0; a < 5; a++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) acc += 2.0 * (double)n[a] * (double)nw[c] * (double)Sm[a][6 + c];
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+#pragma unroll
+                for (int e = 0; e < 3; e++) acc += (double)nw[c] * (double)nw[e] * (double)Sm[6 + c][6 + e];
+        }
+        return (float)acc;
+    };
+    if (live) {
+        const GaussGeom gg = load_geom(g, i);
+        float ca, cb, cc, c3[6];
+        Proj pj;  // (with c3: reused by the unit chain evaluations below)
+        gaussian_conic(cam, g, gg, i, ca, cb, cc, &pj, c3);
+        const float ddx = (float)(0.5 * cam.W), ddy = (float)(0.5 * cam.H);  // backward.cu:935-936
+        // chain input g2 = Lm u: dmean2D (NDC units) from (hx, hy), dconic = -u_conic / 2 (backward.cu:1020-1038)
+        const float L0[2] = {-ca * ddx, -cb * ddx}, L1[2] = {-cb * ddy, -cc * ddy};
+        {
+            const float n0[5] = {L0[0], L0[1], 0.f, 0.f, 0.f}, n1[5] = {L1[0], L1[1], 0.f, 0.f, 0.f};
+            o_m2[0] = qform(n0, nullptr, 0);
+            o_m2[1] = qform(n1, nullptr, 0);
+        }
+        // coefficient rows n = (chain column) Lm, accumulated one unit chain input at a time
+        float nm[3][5], nc[6][5], ns[3][5], nr[4][5], nw[3][3];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+#pragma unroll
+            for (int b = 0; b < 5; b++) nm[r][b] = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; c++) nw[r][c] = 0.f;
+        }
+#pragma unroll 1
+        for (int kk = 0; kk < (MOM == 2 ? 8 : 5); kk++) {
+            const int in = kk < 5 ? kk : kk + 1;
+            float g2[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            g2[in] = 1.f;
+            float dmean[3], dcov[6], dscale[3], drot[4], dsh[48];
+            gauss_chain(cam, g, gg, i, g2, 0u, dmean, dcov, dscale, drot, dsh, nsh, true, &pj, c3);
+            // (selects with constant indices: no dynamic register-array indexing)
+#pragma unroll
+            for (int b = 0; b < 5; b++) {
+                const float lk = kk == 0 ? (b == 0 ? L0[0] : (b == 1 ? L0[1] : 0.f))
+                                         : kk == 1 ? (b == 0 ? L1[0] : (b == 1 ? L1[1] : 0.f))
+                                                   : (kk == b ? -0.5f : 0.f);
+#pragma unroll
+                for (int r = 0; r < 3; r++) nm[r][b] = __builtin_fmaf(dmean[r], lk, nm[r][b]);
+                if (b >= 2) {  // cov3D / scale / rotation depend on the conic terms only
+#pragma unroll
+                    for (int r = 0; r < 6; r++) nc[r][b] = kk == b ? -0.5f * dcov[r] : (kk < 2 ? 0.f : nc[r][b]);
+#pragma unroll
+                    for (int r = 0; r < 3; r++) ns[r][b] = kk == b ? -0.5f * dscale[r] : (kk < 2 ? 0.f : ns[r][b]);
+#pragma unroll
+                    for (int r = 0; r < 4; r++) nr[r][b] = kk == b ? -0.5f * drot[r] : (kk < 2 ? 0.f : nr[r][b]);
+                }
+            }
+            if (MOM == 2 && kk >= 5) {
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+#pragma unroll
+                    for (int r = 0; r < 3; r++) nw[r][c] = (kk - 5 == c) ? dmean[r] : nw[r][c];  // view-direction term
+                if (kk == 5)
+#pragma unroll
+                    for (int k = 0; k < 16; k++) ysq[k] = k < nsh ? dsh[3 * k] * dsh[3 * k] : 0.f;
+            }
+        }
+        clamped = g.shs ? geo.clamp[i] : 0u;
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            float w3[3];
+#pragma unroll
+            for (int c = 0; c < 3; c++) w3[c] = ((clamped >> c) & 1u) ? 0.f : nw[r][c];
+            o_mean[r] = qform(nm[r], w3, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 6; r++) o_cov[r] = qform(nc[r], nullptr, 2);
+        if (g.scales) {  // the reference forms no scale / rotation gradient from a precomputed cov3D
+#pragma unroll
+            for (int r = 0; r < 3; r++) o_scale[r] = qform(ns[r], nullptr, 2);
+#pragma unroll
+            for (int r = 0; r < 4; r++) o_rot[r] = qform(nr[r], nullptr, 2);
+        }
+    }
+    if (out.dmeans2D) {
+        out.dmeans2D[3 * i] = o_m2[0];
+        out.dmeans2D[3 * i + 1] = o_m2[1];
+        out.dmeans2D[3 * i + 2] = 0.f;
+    }
+    if (out.dcolors)
+#pragma unroll
+        for (int c = 0; c < 3; c++) out.dcolors[3 * i + c] = Sm[6 + c][6 + c];
+    if (out.dopacity) out.dopacity[i] = Sm[5][5];
+#pragma unroll
+    for (int r = 0; r < 3; r++) out.dmeans3D[3 * i + r] = o_mean[r];
+    if (out.dcov3D)
+#pragma unroll
+        for (int r = 0; r < 6; r++) out.dcov3D[6 * i + r] = o_cov[r];
+    if (out.dscales)
+#pragma unroll
+        for (int r = 0; r < 3; r++) out.dscales[3 * i + r] = o_scale[r];
+    if (out.drot)
+#pragma unroll
+        for (int r = 0; r < 4; r++) out.drot[4 * i + r] = o_rot[r];
+    if (out.dsh && g.M > 0) {  // dsh[k][c] = Y_k dRGB_c per pair: Y_k^2 sum (dRGB_c)^2, 0 where the colour clamped
+        float* d = out.dsh + (size_t)3 * g.M * i;
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+#pragma unroll
+            for (int c = 0; c < 3; c++)
+                if (k < g.M) d[3 * k + c] = !((clamped >> c) & 1u) ? ysq[k] * Sm[6 + c][6 + c] : 0.f;
+        for (int k = 16; k < g.M; k++)
+            for (int c = 0; c < 3; c++) d[3 * k + c] = 0.f;
+    }
+}
+
+hipError_t launch_gauss_bwd_moments(const Camera& cam, const GaussIn& g, GeomPtrs geo, const int* radii,
+                                    const float* inst, const GradsOut& out, BwdGuard guard, hipStream_t s) {
+    if (g.P == 0) return hipSuccess;
+    auto k = g.shs ? gauss_bwd_mom_kernel<2> : gauss_bwd_mom_kernel<1>;
+    hipLaunchKernelGGL(k, dim3((g.P + 255) / 256), dim3(256), 0, s, cam, g, geo, radii, inst, out, guard);
     return hipGetLastError();
 }
 

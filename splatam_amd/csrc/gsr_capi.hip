@@ -695,7 +695,7 @@ struct Backward {
 
     // backward_power == 2 (the fork's Fisher / Hessian scoring, scripts/ros_handler.py:839-902): each
     // pair's squared outputs are quadratic forms of its base values, so render_bwd forms per-instance
-    // second moments and gauss_bwd_mom applies the forms per Gaussian (gsr_backward.hip).  Outputs
+    // second moments and gauss_bwd_mom applies the forms per Gaussian (gsr_backward_power.hip).  Outputs
     // not requested (NULL) are skipped; dmeans3D is always formed.
     int moments() {
         const bool sh = g.shs != nullptr;

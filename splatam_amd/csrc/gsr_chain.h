@@ -1,5 +1,5 @@
 // gsr_chain.h -- per-Gaussian backward chain shared by the power-1 and the
-// backward_power != 1 pipelines (gsr_backward.hip, gsr_backward_power.hip).
+// backward_power != 1 pipelines (gsr_backward.hip; gsr_backward_power.hip, the second-moment route included).
 #pragma once
 #include "gsr_layout.h"
 #include "gsr_math.h"

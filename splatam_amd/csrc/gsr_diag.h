@@ -13,6 +13,10 @@
 //   GSR_ABLATE / GSR_FWD_ABLATE  timing ablations of the backward / forward render (results invalid);
 //                 GSR_ABLATE is read through kAblate
 //   GSR_DUP_PHASE one render phase run twice, for a VALU census by SQ counters (results unchanged)
+// The counters are static __device__ per translation unit, and the gsr_diag_*_bwd read-backs (gsr_backward.hip)
+// reach that file's copy only.  render_bwd_kernel's two second-moment forms are instantiated by
+// gsr_backward_power.hip, so in a diagnostics build their counts land in that file's copy, which nothing reads
+// back: the tools (tools/phase.py, tools/wgtime.py, tools/stepstat.py) run the power-1 renders.
 // These and RenderDiag are the only build switches of the kernels: the numeric tunables (GSR_BWD_BB ...) fork
 // no code, and an A/B of two implementations is built from two revisions (build.build_from_rev), not from a
 // macro in the sources.

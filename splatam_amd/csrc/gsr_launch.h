@@ -69,6 +69,7 @@ struct EqualPairs {
 };
 hipError_t launch_bitwise_equal(const EqualPairs& q, int* flag, hipStream_t s);
 // ------------------------------------------------------ gsr_backward.hip --
+// (the tile backward its render kernels inline, bwd_tile, and render_bwd_kernel itself: gsr_render_bwd.h)
 // the tracking iteration's forward (+ L1) and render backward in one launch (gsr_backward.hip); inst receives
 // the pose-fused gauss_bwd's per-instance records (track_records_floats)
 hipError_t launch_render_track(const Camera& cam, const uint2* ranges, uint64_t* point_list, uint64_t* keys,
@@ -84,6 +85,35 @@ struct RecLayout {
     int stride;                 // floats per record (even)
     int o_op, o_c1, o_c2, n_c2; // offsets, -1 when absent
 };
+// The one statement of that layout: the record of a variant that forms the opacity sum (op), the colour sums
+// (c1: three slots, also where a tile forms one, bwd_tile's C1 = 1), q2 second-colour sums (c2) and the first
+// colour set's own (hx, hy) pair (m2d).  BwdShape (gsr_render_bwd.h) sizes the tile backward from it, and
+// bwd_rec_layout() hands its `rec` to gauss_bwd.
+struct RecSums {
+    RecLayout rec;
+    int o_col;  // where the colour sums start: the geometric sums and the opacity sum lie before it
+    int o_m1;   // the M2D1 pair, -1 when absent
+    int nv;     // sums per record (stride: nv rounded up to even)
+};
+constexpr RecSums rec_sums(bool op, bool c1, bool c2, int q2, bool m2d = false) {
+    RecSums s{};
+    int nv = 5;
+    s.rec.o_op = op ? nv : -1;
+    nv += op ? 1 : 0;
+    s.o_col = nv;
+    s.rec.o_c1 = c1 ? nv : -1;
+    nv += c1 ? 3 : 0;
+    s.rec.o_c2 = c2 ? nv : -1;
+    s.rec.n_c2 = c2 ? q2 : 0;
+    nv += s.rec.n_c2;
+    s.o_m1 = m2d ? nv : -1;
+    nv += m2d ? 2 : 0;
+    s.nv = nv;
+    s.rec.stride = (nv + 1) & ~1;
+    return s;
+}
+static_assert(rec_sums(true, true, true, 3).rec.stride == INST_REC_MAX && rec_sums(true, true, true, 1, true).nv == INST_REC_MAX,
+              "INST_REC_MAX: the largest records, every sum of a dual render and the M2D1 form");
 RecLayout bwd_rec_layout(unsigned need, bool dual);
 hipError_t launch_render_bwd(const Camera& cam, const uint2* ranges, const uint64_t* point_list, GeomPtrs geo,
                              const float* final_T, const uint32_t* n_contrib, const float* dL_dpix,
@@ -108,7 +138,8 @@ struct GradsOut {
 // record is the mapping variant's ten sums, then the pair at M2D_REC_PAIR: 12 floats, the stated maximum.
 // M2dOut is a record of its own, not a field of RecLayout / GradsOut: those are by-value arguments of every
 // gauss_bwd_kernel instantiation, whose argument layout (and device code) must not move.
-constexpr int M2D_REC_PAIR = 10;
+constexpr int M2D_REC_PAIR = rec_sums(true, true, true, 1, true).o_m1;
+static_assert(M2D_REC_PAIR == 10, "the mapping variant's ten sums, then the pair");
 struct M2dOut {
     float* dmeans2D_c1 = nullptr;  // [P,3]: (x, y) in NDC units like dmeans2D, z written as 0
     int o_m1 = -1;                 // record offset of the pair, -1 when absent
@@ -151,13 +182,6 @@ hipError_t launch_gauss_bwd(const Camera& cam, const GaussIn& g, GeomPtrs geo, c
                             RecLayout rec, const GradsOut& out, BwdGuard guard, hipStream_t s,
                             const PoseFuse* pose = nullptr, unsigned long long* clk = nullptr);
 hipError_t launch_selftest_reduce9(const float* in, float* out, hipStream_t s);
-// backward_power == 2 through per-instance second moments (gsr_backward.hip, gauss_bwd_mom_kernel)
-int moments_record_floats(bool sh);
-hipError_t launch_render_bwd_moments(const Camera& cam, const uint2* ranges, const uint64_t* point_list, GeomPtrs geo,
-                                     const float* final_T, const uint32_t* n_contrib, const float* dL_dpix, bool sh,
-                                     float* inst, BwdGuard guard, hipStream_t s);
-hipError_t launch_gauss_bwd_moments(const Camera& cam, const GaussIn& g, GeomPtrs geo, const int* radii,
-                                    const float* inst, const GradsOut& out, BwdGuard guard, hipStream_t s);
 // ------------------------------------------------------------ gsr_sh.hip --
 // gsr_sh.hip: SH colour stages with LDS-staged, coalesced coefficient traffic
 bool sh_staged(const Camera& cam, const GaussIn& g);
@@ -197,5 +221,13 @@ hipError_t launch_gauss_bwd_fisher(int P, GeomPtrs geo, const int* radii, const 
                                    float* dopacity, BwdGuard guard, hipStream_t s);
 hipError_t launch_gauss_bwd_power(const Camera& cam, const GaussIn& g, GeomPtrs geo, const int* radii,
                                   const float* rec, const GradsOut& out, BwdGuard guard, hipStream_t s);
+// backward_power == 2 through per-instance second moments: render_bwd_kernel's MOM variants (gsr_render_bwd.h,
+// instantiated by gsr_backward_power.hip) and gauss_bwd_mom_kernel
+int moments_record_floats(bool sh);
+hipError_t launch_render_bwd_moments(const Camera& cam, const uint2* ranges, const uint64_t* point_list, GeomPtrs geo,
+                                     const float* final_T, const uint32_t* n_contrib, const float* dL_dpix, bool sh,
+                                     float* inst, BwdGuard guard, hipStream_t s);
+hipError_t launch_gauss_bwd_moments(const Camera& cam, const GaussIn& g, GeomPtrs geo, const int* radii,
+                                    const float* inst, const GradsOut& out, BwdGuard guard, hipStream_t s);
 
 }  // namespace gsr

@@ -39,7 +39,7 @@ O_FULL, O_SMALL, O_DIM = 0.01, 0.1412, 0.0194
 O_STOP, O_BLOCKER = 0.93, 0.97
 POPCOUNT = dict(full=16, flat=16, block=1, pair=2, quad=4)
 
-# Batch size BB and slot budget BS of every render-backward variant (csrc/gsr_backward.hip bwd_batch() /
+# Batch size BB and slot budget BS of every render-backward variant (csrc/gsr_render_bwd.h bwd_batch() /
 # bwd_slots(), render_bwd_fisher_kernel and PowerShape::BATCH in csrc/gsr_backward_power.hip; the power
 # path has no slot budget).  test_edge_scenes_cpu.py::test_budget_table_matches_sources reads the sources.
 BUDGETS = {

@@ -99,7 +99,7 @@ def test_budget_table_matches_sources():
     """edge_scenes.BUDGETS restates the kernels' batch sizes and slot budgets: read the defaults out of the
     sources, so that a retuned budget cannot leave the edge scenes beside their edges unnoticed."""
     csrc = os.path.join(ROOT, "splatam_amd", "csrc")
-    bwd = open(os.path.join(csrc, "gsr_backward.hip")).read()
+    bwd = open(os.path.join(csrc, "gsr_render_bwd.h")).read()
     pw = open(os.path.join(csrc, "gsr_backward_power.hip")).read()
     common = open(os.path.join(csrc, "gsr_layout.h")).read()
     BB = int(_define(bwd, "GSR_BWD_BB"))

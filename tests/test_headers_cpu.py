@@ -4,7 +4,8 @@ Needs hipcc and no GPU (skipped without hipcc).  Every csrc/*.h compiles on its 
 gsr_common.h, which the headers were cut from, is gone; the files that launch no render kernel do not reach
 gsr_launch.h (read from the preprocessor's dependency output, not from the source text); and adam_coef
 (csrc/gsr_adam.h), called from a stand-alone host program, returns bit for bit the five floats the three fills
-it replaced computed.
+it replaced computed; and rec_sums (csrc/gsr_launch.h), likewise from a host program, gives the instance record
+layouts the three statements it replaced gave.
 """
 import glob
 import math
@@ -53,6 +54,86 @@ def test_does_not_reach_the_launchers(hipcc, name):
     deps = {os.path.basename(d) for d in r.stdout.replace("\\\n", " ").split()}
     assert "gsr_layout.h" in deps or "gsr_wave.h" in deps, deps  # (the output does list the csrc headers)
     assert "gsr_launch.h" not in deps
+
+
+LAYOUT_MAIN = r"""
+#include <stdio.h>
+
+#include "gsr_render_bwd.h"
+
+using namespace gsr;
+// NV, RS and bytes of the parent's positional BwdShape instantiations (printed by a one-off program compiled
+// against the parent's gsr_backward.hip)
+#define SHAPE_IS(V, nv, rs, by) \
+    static_assert(BwdShape<V>::NV == nv && BwdShape<V>::RS == rs && BwdShape<V>::bytes == by, #V)
+SHAPE_IS(TrackVariant, 6, 6, 28064);       // BwdShape<true, false, false, true, 1, 0>
+SHAPE_IS(MapM2dVariant, 12, 12, 34224);    // BwdShape<true, true, true, true, 1, 0, 3, true>
+SHAPE_IS(MomVariant<1>, 16, 16, 32192);    // BwdShape<false, true, true, false, 3, 1>
+SHAPE_IS(MomVariant<2>, 34, 34, 33296);    // BwdShape<false, true, true, false, 3, 2>
+using Full1 = BwdVariant<false, true, true, false>;
+using Col1 = BwdVariant<false, false, true, false>;
+SHAPE_IS(Full1, 9, 10, 29616);             // BwdShape<false, true, true, false, 3, 0>
+SHAPE_IS(OneColour<Full1>, 7, 10, 26528);  // BwdShape<false, true, true, false, 3, 0, 1>
+SHAPE_IS(OneColour<Col1>, 6, 8, 24992);    // BwdShape<false, false, true, false, 3, 0, 1>
+
+static void row(const char* tag, int a, int b, const RecSums& s) {
+    printf("%s %d %d %d %d %d %d %d %d %d\n", tag, a, b, s.rec.stride, s.rec.o_op, s.rec.o_c1, s.rec.o_c2, s.rec.n_c2,
+           s.o_m1, s.nv);
+}
+int main() {
+    for (int dual = 0; dual < 2; dual++)
+        for (unsigned need = 0; need < 16; need++)  // launch_render_bwd's decoding of (need, dual): bwd_terms()
+            row("rec", dual, (int)need,
+                rec_sums((need & NEED_OPACITY) != 0, (need & NEED_COLORS) != 0, dual && (need & NEED_COLORS2),
+                         (dual && (need & NEED_DL2_CH0_ONLY)) ? 1 : 3));
+    row("m2d", 1, 0, bwd_sums<MapM2dVariant>());
+    printf("const %d %d\n", M2D_REC_PAIR, INST_REC_MAX);
+    return 0;
+}
+"""
+
+# (dual, need) -> (stride, o_op, o_c1, o_c2, n_c2, sums): the parent's bwd_rec_layout arithmetic -- five geometric
+# sums, then the opacity sum (+1), the colour sums (+3) and the second colour set's (+q2, with a second image
+# only; q2 = 1 under NEED_DL2_CH0_ONLY); absent terms -1; the stride is the count rounded up to even.
+# need: NEED_OPACITY 1, NEED_COLORS 2, NEED_COLORS2 4, NEED_DL2_CH0_ONLY 8.
+REC_LAYOUTS = {
+    (0, 0): (6, -1, -1, -1, 0, 5), (0, 1): (6, 5, -1, -1, 0, 6), (0, 2): (8, -1, 5, -1, 0, 8),
+    (0, 3): (10, 5, 6, -1, 0, 9), (0, 4): (6, -1, -1, -1, 0, 5), (0, 5): (6, 5, -1, -1, 0, 6),
+    (0, 6): (8, -1, 5, -1, 0, 8), (0, 7): (10, 5, 6, -1, 0, 9), (0, 8): (6, -1, -1, -1, 0, 5),
+    (0, 9): (6, 5, -1, -1, 0, 6), (0, 10): (8, -1, 5, -1, 0, 8), (0, 11): (10, 5, 6, -1, 0, 9),
+    (0, 12): (6, -1, -1, -1, 0, 5), (0, 13): (6, 5, -1, -1, 0, 6), (0, 14): (8, -1, 5, -1, 0, 8),
+    (0, 15): (10, 5, 6, -1, 0, 9),
+    (1, 0): (6, -1, -1, -1, 0, 5), (1, 1): (6, 5, -1, -1, 0, 6), (1, 2): (8, -1, 5, -1, 0, 8),
+    (1, 3): (10, 5, 6, -1, 0, 9), (1, 4): (8, -1, -1, 5, 3, 8), (1, 5): (10, 5, -1, 6, 3, 9),
+    (1, 6): (12, -1, 5, 8, 3, 11), (1, 7): (12, 5, 6, 9, 3, 12), (1, 8): (6, -1, -1, -1, 0, 5),
+    (1, 9): (6, 5, -1, -1, 0, 6), (1, 10): (8, -1, 5, -1, 0, 8), (1, 11): (10, 5, 6, -1, 0, 9),
+    (1, 12): (6, -1, -1, 5, 1, 6), (1, 13): (8, 5, -1, 6, 1, 7), (1, 14): (10, -1, 5, 8, 1, 9),
+    (1, 15): (10, 5, 6, 9, 1, 10),
+}
+M2D_LAYOUT = (12, 5, 6, 9, 1, 10, 12)  # the mapping record (1, 15), then the pair at 10: stride 12
+
+
+def test_record_layout_is_the_parents(hipcc, tmp_path):
+    """rec_sums (csrc/gsr_launch.h), the one statement of the instance record's layout, gives for every
+    (need, dual) launch_render_bwd accepts and for the M2D form what the three statements it replaced gave
+    (bwd_nv, bwd_tile's O_C1 / NA / NB and bwd_rec_layout's run-time arithmetic, all in the parent's
+    gsr_backward.hip), and BwdShape of every named variant keeps its sums, record stride and LDS bytes (the
+    program's static_asserts)."""
+    src, exe = tmp_path / "layout_main.hip", tmp_path / "layout_main"
+    src.write_text(LAYOUT_MAIN)
+    r = _run([hipcc, *build.flags(), "--cuda-host-only", str(src), "-o", str(exe)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = _run([str(exe)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    rows = [ln.split() for ln in r.stdout.splitlines()]
+    rec = {(int(w[1]), int(w[2])): tuple(int(x) for x in w[3:]) for w in rows if w[0] == "rec"}
+    assert set(rec) == set(REC_LAYOUTS)
+    for key, (stride, o_op, o_c1, o_c2, n_c2, nv) in REC_LAYOUTS.items():
+        assert rec[key] == (stride, o_op, o_c1, o_c2, n_c2, -1, nv), key
+    m2d = [tuple(int(x) for x in w[3:]) for w in rows if w[0] == "m2d"]
+    assert m2d == [M2D_LAYOUT]
+    assert [w[1:] for w in rows if w[0] == "const"] == [["10", "12"]]
+    assert max(v[0] for v in REC_LAYOUTS.values()) == M2D_LAYOUT[0] == 12
 
 
 ADAM_MAIN = r"""

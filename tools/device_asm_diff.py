@@ -6,8 +6,10 @@ and compares the two texts function by function: a function's body and, for a ke
 descriptor block (registers, LDS, scratch, kernarg size).  Labels carry the function's index in its file
 (.LBB<i>_<n>, .Lfunc_end<i>, `BB<i>_<n>` in the loop comments), which moves when a function is added ahead of it, so the index is dropped before
 comparing.  Prints per file `identical` or the functions whose text differs, and the functions only one side has
-(`added` / `removed`); exits non-zero when a function both sides have differs or one was removed.  With functions
-added, the text outside any function (the metadata listing every kernel) differs by construction and is not
+(`added` / `removed`); a function one file lost and another file gained is looked up by name across all files of
+the other side and printed under its new file as `moved from X to Y: identical` or `differs`.  Exits non-zero when
+a function both sides have differs, in place or moved, or one was removed.  With functions added, removed or moved,
+the file's text outside any function (the metadata listing every kernel) differs by construction and is not
 compared; without, it is.  Needs hipcc, no GPU.
 """
 import os
@@ -61,11 +63,17 @@ def main():
                 lambda j: device_asm(j[0], *trees[j[1]], os.path.join(work, f"{j[1]}_{j[0]}.s")), jobs)))
     finally:
         shutil.rmtree(work, ignore_errors=True)
+    funcs = {(src, side): functions(asm[src, side]) for src in build.SOURCES for side in trees}
+    # a function one file lost and another gained has moved: looked up by name across the other side's files
+    home = {side: {f: src for src in build.SOURCES for f in funcs[src, side] if f} for side in trees}
     bad = 0
     for src in build.SOURCES:
-        old, new = functions(asm[src, "old"]), functions(asm[src, "new"])
-        added, removed = sorted(new.keys() - old.keys()), sorted(old.keys() - new.keys())
-        both = [f for f in old.keys() & new.keys() if f or not (added or removed)]
+        old, new = funcs[src, "old"], funcs[src, "new"]
+        gained, lost = sorted(new.keys() - old.keys()), sorted(old.keys() - new.keys())
+        moved_in = [f for f in gained if home["old"].get(f, src) != src]
+        moved_out = [f for f in lost if home["new"].get(f, src) != src]
+        added, removed = sorted(set(gained) - set(moved_in)), sorted(set(lost) - set(moved_out))
+        both = [f for f in old.keys() & new.keys() if f or not (gained or lost)]
         diff = sorted(f or "(outside any function)" for f in both if old[f] != new[f])
         bad += bool(diff or removed)
         text = "differs in " + ", ".join(diff) if diff else f"identical ({len(both)} functions)"
@@ -73,6 +81,10 @@ def main():
             if names:
                 text += f"; {what}: " + ", ".join(names)
         print(f"{src}: {text}")
+        for f in moved_in:
+            same = funcs[home["old"][f], "old"][f] == new[f]
+            bad += not same
+            print(f"  {f} moved from {home['old'][f]} to {src}: {'identical' if same else 'differs'}")
     return 1 if bad else 0
 
 
