@@ -385,6 +385,14 @@ int gsr_forward_dual_static_alive(const gsr_settings* settings, const gsr_gaussi
                                   int capacity, unsigned* status, float* out_color, float* out_color2,
                                   float* out_depth, int* radii, const unsigned char* alive, gsr_alloc_fn alloc,
                                   void* alloc_ctx, void* stream);
+/* The single-image counterpart: gsr_forward_static (include/gsr.h) with the same mask and the same rule --
+ * alive[i] == 0 culls Gaussian i (radius 0, no instances, zero gradients from gsr_backward), the others'
+ * image, depth, radii, status counters and gradients are exactly those of gsr_forward_static on the compacted
+ * set.  alive == NULL with P > 0 is GSR_ERR_INVALID_ARG ("alive mask required"), after the static-mode check.
+ * The view scorer of a capacity-padded map renders through it (splatam_amd.fisher.SequenceFisher). */
+int gsr_forward_static_alive(const gsr_settings* settings, const gsr_gaussians* gaussians, int capacity,
+                             unsigned* status, float* out_color, float* out_depth, int* radii,
+                             const unsigned char* alive, gsr_alloc_fn alloc, void* alloc_ctx, void* stream);
 
 /* The mapping iteration's transform fused into its forward (as
  * gsr_track_forward_dual_static_xf for tracking): gsr_track_transform_fwd(xform -> gaussians->means3D,
@@ -435,6 +443,32 @@ int gsr_adam_step(int n_tensors, const gsr_adam_tensor* tensors, int step, doubl
 int gsr_points_to_camera(int P, const float* means, const float* w2c, float* pts, void* stream);
 int gsr_fisher_accumulate(int P, const float* dmeans3D, const float* dopacity, const float* weight, float* H,
                           void* stream);
+
+/* compute_eig_score (scripts/ros_handler.py:832-836), torch.sum(cur_H * H_train_inv), of one pose in one
+ * launch, from the two gradients the power-2 backward left:
+ *     *out = sum over the rows i with alive[i] != 0 (every row when alive == NULL) and c = 0..3 of
+ *            (double) fl32(H[i,c] * H_inv[i,c]),  H[i,0..2] = dmeans3D[i,0..2], H[i,3] = dopacity[i].
+ * dmeans3D [P,3], dopacity [P,1], H_inv [P,4] (16-byte aligned), alive uint8 [P] or NULL, out: one double
+ * (device, 8-byte aligned).  Each product is rounded to float32 once, as the reference's elementwise product
+ * is, and is not contracted into the sum; the sum is accumulated in float64.  A dead row is selected out, not
+ * multiplied by zero: its H and H_inv may hold anything (NaN included) and do not reach the result -- the
+ * rows of a capacity-padded map under its alive mask (splatam_amd.sequence).
+ *   Order: at most 256 workgroups of 256 threads stride over the rows; a thread adds its rows in ascending
+ * order (the four columns in order), a workgroup adds its threads by a lane tree and then its four waves,
+ * and the last workgroup to arrive adds the workgroups' partials by the same tree over the workgroup index.
+ * No float atomic: the same inputs (and the same P) give the same bits on every call.  The float64 sum of
+ * n = 4 P non-negative terms in any order is within (n - 1) 2^-53 of the exact sum, relative.
+ *   P == 0: *out = 0.0, no other pointer is read.  Everything is enqueued on `stream` (one launch) and
+ * nothing waits on the host, so the call can be captured in a graph.
+ * workspace: gsr_fisher_score_workspace_bytes() bytes of its own (a constant: the grid is bounded; not the
+ * reduction scratch above), 16-byte aligned, zero-filled once before its first use: its arrival counter
+ * (word 0, whatever P) returns to zero and the partials are written before they are read, so one buffer
+ * serves any number of calls of any P on one stream; calls that may run concurrently need their own.
+ * Refused with GSR_ERR_INVALID_ARG, nothing enqueued: P < 0, a NULL or misaligned out, and with P > 0 a NULL
+ * dmeans3D, dopacity, H_inv or workspace, or a misaligned H_inv or workspace. */
+size_t gsr_fisher_score_workspace_bytes(void);
+int gsr_fisher_score(int P, const float* dmeans3D, const float* dopacity, const float* H_inv,
+                     const unsigned char* alive, void* workspace, double* out, void* stream);
 
 /* The silhouette half of the fork's mixed view gain (scripts/ros_handler.py:251-359, send_gains:
  * g_sil = (sil < 0.5).sum() / (W H) of a second, depth/silhouette render per candidate pose,

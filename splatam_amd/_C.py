@@ -340,13 +340,16 @@ def _remember(key, shared, others, bufs, radii, num_rendered):
 
 def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
                         viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
-                        prefiltered, capacity=0, status=None):
+                        prefiltered, capacity=0, status=None, alive=None):
     """RasterizeGaussiansCUDA (rasterize_points.cu:35-115).
 
     Returns (num_rendered, color[3,H,W], radii[P] int32, geomBuffer, binningBuffer, imgBuffer, depth[1,H,W]).
     capacity > 0 selects gsr_forward_static (no host synchronisation, HIP-graph capturable; `status` is a
-    device int32[4] receiving the sticky counters, and num_rendered is the capacity).
+    device int32[4] receiving the sticky counters, and num_rendered is the capacity).  alive (static mode
+    only): a device uint8 [P] mask, 0 = culled (gsr_forward_static_alive: radius 0, no instances).
     """
+    if capacity <= 0 and alive is not None:
+        raise RuntimeError("the alive mask and the fused transform need the static (capacity > 0) forward")
     if (_NATIVE_ON and capacity <= 0 and binning_mode() == BINNING_CULLED and _native() is not None):
         return _native().rasterize_gaussians(
             _t(background), means3D, _t(colors), _t(opacity), _t(scales), _t(rotations), float(scale_modifier),
@@ -408,9 +411,15 @@ def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations,
         _begin(device)
         if capacity > 0:
             _check_status(status, device)
-            n = lib.gsr_forward_static(ctypes.byref(s), ctypes.byref(g), int(capacity), status.data_ptr(),
-                                       out_color.data_ptr(), out_depth.data_ptr(), radii.data_ptr(), _ALLOC_CB, None,
-                                       stream)
+            _check_alive(alive, P, device)
+            if alive is not None:
+                n = lib.gsr_forward_static_alive(ctypes.byref(s), ctypes.byref(g), int(capacity), status.data_ptr(),
+                                                 out_color.data_ptr(), out_depth.data_ptr(), radii.data_ptr(),
+                                                 alive.data_ptr(), _ALLOC_CB, None, stream)
+            else:
+                n = lib.gsr_forward_static(ctypes.byref(s), ctypes.byref(g), int(capacity), status.data_ptr(),
+                                           out_color.data_ptr(), out_depth.data_ptr(), radii.data_ptr(), _ALLOC_CB,
+                                           None, stream)
         else:
             n = lib.gsr_forward(ctypes.byref(s), ctypes.byref(g), out_color.data_ptr(), out_depth.data_ptr(),
                                 radii.data_ptr(), _ALLOC_CB, None, stream)

@@ -193,6 +193,9 @@ SIGNATURES = {
     "gsr_forward_dual_static_alive": (c_int, [ctypes.POINTER(GsrSettings), ctypes.POINTER(GsrGaussians), c_void_p,
                                               c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               ALLOC_FN, c_void_p, c_void_p]),
+    # (gsr_forward_static's arguments with `alive` behind `radii`)
+    "gsr_forward_static_alive": (c_int, [ctypes.POINTER(GsrSettings), ctypes.POINTER(GsrGaussians), c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, ALLOC_FN, c_void_p, c_void_p]),
     "gsr_forward_dual_static_xf": (c_int, [ctypes.POINTER(GsrSettings), ctypes.POINTER(GsrGaussians), c_void_p,
                                            ctypes.POINTER(GsrTrackXform), c_int, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, ALLOC_FN, c_void_p, c_void_p]),
@@ -202,6 +205,8 @@ SIGNATURES = {
     "gsr_fisher_accumulate": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gsr_silhouette_count": (c_int, [ctypes.POINTER(GsrSettings), c_int, c_int, c_void_p, c_void_p, c_void_p, c_float,
                                      c_void_p, c_void_p]),
+    "gsr_fisher_score_workspace_bytes": (c_size_t, []),
+    "gsr_fisher_score": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # include/gsr_glue.h: overlap keyframe selection
     "gsr_keyframe_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gsr_keyframe_select": (c_int, [c_int, c_int, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_void_p,

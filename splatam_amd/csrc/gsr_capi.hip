@@ -989,6 +989,16 @@ int gsr_forward_dual_static_alive(const gsr_settings* settings, const gsr_gaussi
     return forward_impl(statics(dual(c, colors2, out_color2), capacity, status));
 }
 
+int gsr_forward_static_alive(const gsr_settings* settings, const gsr_gaussians* gaussians, int capacity,
+                             unsigned* status, float* out_color, float* out_depth, int* radii,
+                             const unsigned char* alive, gsr_alloc_fn alloc, void* alloc_ctx, void* stream) {
+    if (capacity <= 0 || !status) return fail(GSR_ERR_INVALID_ARG, "static mode needs capacity > 0 and status");
+    if (!alive && gaussians && gaussians->P > 0) return fail(GSR_ERR_INVALID_ARG, "alive mask required");
+    FwdCall c = fwd_call(settings, gaussians, out_color, out_depth, radii, alloc, alloc_ctx, stream);
+    c.alive = alive;
+    return forward_impl(statics(c, capacity, status));
+}
+
 int gsr_forward_dual_static_xf(const gsr_settings* settings, const gsr_gaussians* gaussians, float* colors2,
                                const gsr_track_xform* xform, int capacity, unsigned* status, float* out_color,
                                float* out_color2, float* out_depth, int* radii, gsr_alloc_fn alloc, void* alloc_ctx,

@@ -25,6 +25,17 @@
 //
 // Counting: a wave's ballot of the counted pixels, its popcount through LDS, one integer atomic per
 // workgroup: the same word whatever the arrival order.
+//
+// The EIG half (compute_eig_score, :832-836) of one pose in one launch (include/gsr_glue.h: gsr_fisher_score):
+//
+//   fisher_score_kernel      at most FS_MAX_BLOCKS workgroups of 256 threads stride over the rows (a 300 k-row
+//                            map is 10 MB of reads: the launch is bound by latency, not by bandwidth, so one
+//                            workgroup per CU and a single arrival counter).  A row's four products are rounded
+//                            to float32 (no contraction) and added to the thread's float64 sum in column order;
+//                            a dead row is skipped, its values never enter an operation.  The workgroup's sum
+//                            (lane tree, then the four waves) goes to the workspace; the last workgroup to arrive
+//                            adds the partials in workgroup order and writes the score.  No float atomics: the
+//                            same inputs give the same bits.
 #include <stdint.h>
 
 #include "../../include/gsr.h"
@@ -144,6 +155,50 @@ silhouette_count_kernel(Camera cam, const uint2* __restrict__ ranges, const Poin
     }
 }
 
+constexpr int FS_BLOCK = 256;
+constexpr int FS_MAX_BLOCKS = 256;      // one workgroup per CU; each thread of the last one gathers one partial
+constexpr size_t FS_HEAD_BYTES = 128;   // the arrival counter (word 0; zero between calls), nothing else
+
+// Sums v over the workgroup in a fixed order (the wave's lane tree, then the four waves); every thread
+// returns with the sum.
+__device__ __forceinline__ double fs_block_sum(double v, double* s_red /*FS_BLOCK / 64*/) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
+    __syncthreads();  // (an earlier call's readers are done with s_red)
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
+__global__ void __launch_bounds__(FS_BLOCK)
+fisher_score_kernel(int P, const float* __restrict__ dmeans, const float* __restrict__ dopac,
+                    const float4* __restrict__ hinv, const uint8_t* __restrict__ alive, uint32_t* counter,
+                    double* part, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ double s_red[FS_BLOCK / 64];
+    const int tid = threadIdx.x;
+    double acc = 0.;
+    for (long long i = (long long)blockIdx.x * FS_BLOCK + tid; i < P; i += (long long)gridDim.x * FS_BLOCK) {
+        if (alive != nullptr && alive[i] == 0) continue;  // selected out: a dead row's values are never read
+        const float4 hi = hinv[i];
+        const float h0 = dmeans[3 * i], h1 = dmeans[3 * i + 1], h2 = dmeans[3 * i + 2], h3 = dopac[i];
+        const float p0 = h0 * hi.x, p1 = h1 * hi.y, p2 = h2 * hi.z, p3 = h3 * hi.w;
+        acc += (double)p0;
+        acc += (double)p1;
+        acc += (double)p2;
+        acc += (double)p3;
+    }
+    acc = fs_block_sum(acc, s_red);
+    if (tid == 0) st_agent(part + blockIdx.x, acc);
+    if (!last_block_arrive(counter)) return;
+    const int nb = gridDim.x;  // <= FS_MAX_BLOCKS == FS_BLOCK: thread b holds workgroup b's partial
+    acc = tid < nb ? ld_agent(part + tid) : 0.;
+    acc = fs_block_sum(acc, s_red);
+    if (tid == 0) *out = acc;
+}
+
+__global__ void set_double_kernel(double* __restrict__ p, double v) { *p = v; }
+
 }  // namespace
 }  // namespace gsr
 
@@ -197,6 +252,33 @@ int gsr_silhouette_count(const gsr_settings* settings, int P, int num_rendered, 
                        point_list, geo.rr, BwdGuard{geo.counters, (uint32_t)num_rendered}, sil_thres, count);
     e = hipGetLastError();
     return e == hipSuccess ? GSR_OK : hip_fail(e, "silhouette_count");
+}
+
+size_t gsr_fisher_score_workspace_bytes(void) { return FS_HEAD_BYTES + 8 * (size_t)FS_MAX_BLOCKS; }
+
+int gsr_fisher_score(int P, const float* dmeans3D, const float* dopacity, const float* H_inv,
+                     const unsigned char* alive, void* workspace, double* out, void* stream_) {
+    static_assert(FS_MAX_BLOCKS <= FS_BLOCK, "the last workgroup gathers one partial per thread");
+    if (P < 0) return fail(GSR_ERR_INVALID_ARG, "fisher_score: P must be >= 0");
+    if (!out) return fail(GSR_ERR_INVALID_ARG, "fisher_score: null out pointer");
+    if (((uintptr_t)out & 7u) != 0) return fail(GSR_ERR_INVALID_ARG, "fisher_score: out must be 8-byte aligned");
+    hipStream_t stream = (hipStream_t)stream_;
+    hipError_t e;
+    if (P == 0) {  // the empty sum (no pointer but out is read)
+        hipLaunchKernelGGL(set_double_kernel, dim3(1), dim3(1), 0, stream, out, 0.0);
+        e = hipGetLastError();
+        return e == hipSuccess ? GSR_OK : hip_fail(e, "fisher_score");
+    }
+    if (!dmeans3D || !dopacity || !H_inv || !workspace) return fail(GSR_ERR_INVALID_ARG, "fisher_score: null pointer");
+    if (((uintptr_t)H_inv & 15u) != 0 || ((uintptr_t)workspace & 15u) != 0)
+        return fail(GSR_ERR_INVALID_ARG, "fisher_score: H_inv and workspace must be 16-byte aligned");
+    const int need = (int)(((long long)P + FS_BLOCK - 1) / FS_BLOCK);
+    const int nb = need < FS_MAX_BLOCKS ? need : FS_MAX_BLOCKS;
+    hipLaunchKernelGGL(fisher_score_kernel, dim3(nb), dim3(FS_BLOCK), 0, stream, P, dmeans3D, dopacity,
+                       (const float4*)H_inv, alive, (uint32_t*)workspace, (double*)((char*)workspace + FS_HEAD_BYTES),
+                       out);
+    e = hipGetLastError();
+    return e == hipSuccess ? GSR_OK : hip_fail(e, "fisher_score");
 }
 
 }  // extern "C"

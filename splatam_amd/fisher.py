@@ -33,6 +33,13 @@ gain, the share of pixels whose rendered silhouette is below 0.5, which the refe
 second render per pose (get_renders, :955-985) and reads back.  silhouette_count() and
 BatchedFisher(mode="gains") take it from the buffers the scoring forward leaves anyway
 (gsr_silhouette_count, csrc/gsr_viewgain.hip), so each pose is binned once and nothing is read back.
+
+The node scores after every frame of the realtime loop, on the map as it then stands
+(scripts/splatam_realtime.py:1011).  SequenceFisher is BatchedFisher on a running SlamSequence's
+capacity-padded map: captured once, it reads the sequence's own tensors under the alive mask on every
+replay (gsr_forward_static_alive; gsr_fisher_score for the EIG, a float64 sum over the live rows in one
+launch), so a frame's densification, pruning and compaction need no rebuild
+(SlamSequence.view_scorer / fit_visited / view_gains).
 """
 from __future__ import annotations
 
@@ -421,6 +428,199 @@ class BatchedFisher:
         if eig is None:
             return None
         cam = self.sc.cam
+        return combine_gains(self.counts[:len(w2cs)], eig, cam.image_width * cam.image_height, k_sil, k_eig, k_sum,
+                             nl_sil, nl_eig)
+
+    def overflowed(self, n: int | None = None) -> bool:
+        """True if a replay since the last status reset exceeded the capacity in one of the first `n`
+        slots (default: all K; padded slots render the previous poses and are not results)."""
+        st = self.status[: self.K if n is None else n].cpu()
+        return bool((st[:, 0] > self.capacity).any() or (st[:, 2] > st[:, 3]).any() or (st[:, 1] != 0).any())
+
+
+def fisher_score(dmeans: torch.Tensor, dopac: torch.Tensor, H_inv: torch.Tensor, alive, workspace: torch.Tensor,
+                 out: torch.Tensor):
+    """gsr_fisher_score: out (device float64, one element) = the float64 sum over the live rows of the float32
+    products [dmeans, dopac] * H_inv -- compute_eig_score in one launch, nothing read back.  alive: uint8 [P] or
+    None (every row); workspace: score_workspace()'s."""
+    from ._lib import lib
+    P = dmeans.shape[0]
+    dev = out.device
+    for name, t, n in (("dmeans", dmeans, 3 * P), ("dopac", dopac, P), ("H_inv", H_inv, 4 * P)):
+        if t.device != dev or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"fisher_score: {name} must be a contiguous float32 tensor of {n} values on {dev}")
+    if alive is not None and (alive.device != dev or alive.dtype != torch.uint8 or alive.numel() != P or
+                              not alive.is_contiguous()):
+        raise RuntimeError("fisher_score: alive must be a contiguous uint8 tensor of P entries")
+    if out.dtype != torch.float64 or out.numel() != 1:
+        raise RuntimeError("fisher_score: out is one float64")
+    if workspace.device != dev or workspace.numel() * workspace.element_size() < lib.gsr_fisher_score_workspace_bytes():
+        raise RuntimeError("fisher_score: workspace too small (score_workspace)")
+    ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None  # noqa: E731
+    rc = lib.gsr_fisher_score(int(P), ptr(dmeans), ptr(dopac), ptr(H_inv), ptr(alive), workspace.data_ptr(),
+                              out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise RuntimeError(f"gsr_fisher_score: {lib.gsr_last_error().decode(errors='replace')}")
+
+
+def score_workspace(device) -> torch.Tensor:
+    """gsr_fisher_score's workspace: zero-filled once; serves any number of calls on one stream."""
+    from ._lib import lib
+    return torch.zeros(int(lib.gsr_fisher_score_workspace_bytes()), dtype=torch.uint8, device=device)
+
+
+class SequenceFisher:
+    """BatchedFisher on a running sequence's capacity-padded map (splatam_amd.sequence), captured once for the
+    life of the buffers: K poses per HIP-graph launch, read from the map in place.
+
+    params: the sequence's own tensors (`capacity + 1` rows each; means3D, rgb_colors, unnorm_rotations,
+    logit_opacities, log_scales), alive: its uint8 mask, cam: the scoring camera, bin_capacity: the binning
+    capacity of every pose's forward (given, not probed: the sequence sizes it once for all its renders).
+    Every replay forms the rendervars from the tensors as they then stand (the torch ops of
+    FisherScorer.__init__: elementwise per row, so a live row gets the bits it has on the compact map), then
+    per pose slot camera_points, the static forward under the alive mask (gsr_forward_static_alive), in mode
+    "gains" gsr_silhouette_count, the power-2 backward (FISHER_NEEDS) and gsr_fisher_accumulate (mode "sum")
+    or gsr_fisher_score (modes "scores" / "gains"; float64 straight from the kernel, dead rows selected out).
+    So densification, pruning and compact_static between replays need no rebuild; only a map moved to other
+    buffers (SlamSequence.ensure_headroom) does.  The live rows' Hessians are bitwise BatchedFisher's on the
+    compacted map and the dead rows' are +0 (tests/test_gpu_seqscore.py).  Mode "gains" takes the isotropic
+    map only, as BatchedFisher does; overflowed() and the None of a checked call are BatchedFisher's too."""
+
+    def __init__(self, params: dict, alive: torch.Tensor, cam, K: int, mode: str = "sum", bin_capacity: int = 0,
+                 sil_thres: float = 0.5):
+        if mode not in ("sum", "scores", "gains"):
+            raise ValueError("mode is 'sum', 'scores' or 'gains'")
+        if mode == "gains" and params["log_scales"].shape[-1] != 1:
+            raise ValueError("mode 'gains' takes an isotropic map only (log_scales [P,1]): the reference's "
+                             "silhouette render rotates the Gaussians, its Hessian render does not")
+        if int(K) < 1 or int(bin_capacity) <= 0:
+            raise ValueError("SequenceFisher: K >= 1 and bin_capacity > 0 (the static forward's binning capacity)")
+        means = params["means3D"]
+        dev, P = means.device, means.shape[0]
+        if dev.type != "cuda":
+            raise RuntimeError("Fisher scoring runs on ROCm devices only (no CPU fallback)")
+        if alive.dtype != torch.uint8 or alive.numel() != P or alive.device != dev or not alive.is_contiguous():
+            raise RuntimeError("alive: contiguous uint8 [P] on the parameters' device")
+        from . import _C
+        self.params, self.alive, self.cam = params, alive, cam
+        self.K, self.mode, self.capacity, self.sil_thres = int(K), mode, int(bin_capacity), float(sil_thres)
+        self.w2c = torch.eye(4, device=dev).repeat(self.K, 1, 1).contiguous()
+        self.weight = torch.zeros(self.K, device=dev)
+        self.H_inv = torch.zeros(P, 4, device=dev)
+        self.status = torch.zeros(self.K, 4, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(self.K, dtype=torch.int32, device=dev) if mode == "gains" else None
+        self.seed = torch.full((3, cam.image_height, cam.image_width), SEED, device=dev)  # ros_handler.py:888
+        self.e = torch.Tensor([])
+        if mode != "sum":
+            self.out = torch.zeros(self.K, dtype=torch.float64, device=dev)
+            self.workspace = score_workspace(dev)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._body(_C)  # warm-up (allocator pools, kernels) outside the capture
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.status.zero_()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=side):
+            self._body(_C)
+
+    def _rendervars(self):
+        """The map's rendervars as FisherScorer.__init__ forms them (ros_handler.py:868-874), once per replay."""
+        p = self.params
+        rot = F.normalize(p["unnorm_rotations"].detach())
+        opac = torch.sigmoid(p["logit_opacities"].detach())
+        scales = torch.exp(p["log_scales"].detach())
+        scales = torch.tile(scales, (1, 3)) if scales.shape[-1] == 1 else scales
+        return p["means3D"].detach(), p["rgb_colors"].detach(), opac, scales, rot
+
+    def _grads(self, _C, k, rv):
+        """(dL/dmeans_cam [P,3], dL/dopacity [P,1]) of pose slot k (power-2 backward, Fisher kernels)."""
+        cam = self.cam
+        means, colors, opac, scales, rot = rv
+        pts = camera_points(means, self.w2c[k])
+        n, _, radii, geom, binning, img, _ = _C.rasterize_gaussians(
+            cam.bg, pts, colors, opac, scales, rot, cam.scale_modifier, self.e, cam.viewmatrix, cam.projmatrix,
+            cam.tanfovx, cam.tanfovy, cam.image_height, cam.image_width, self.e, cam.sh_degree, cam.campos,
+            cam.prefiltered, capacity=self.capacity, status=self.status[k], alive=self.alive)
+        if self.mode == "gains":  # the silhouette count on this forward's lists, ahead of the backward
+            _count_into(cam, pts.shape[0], n, geom, binning, img, self.sil_thres, self.counts[k:k + 1])
+        g = _C.rasterize_gaussians_backward(cam.bg, pts, radii, colors, scales, rot, cam.scale_modifier, self.e,
+                                            cam.viewmatrix, cam.projmatrix, cam.tanfovx, cam.tanfovy, self.seed,
+                                            self.e, cam.sh_degree, cam.campos, geom, n, binning, img, 2,
+                                            needs=FISHER_NEEDS)
+        return g[3], g[2]
+
+    def _body(self, _C):
+        from ._lib import lib
+        with torch.no_grad():
+            rv = self._rendervars()
+            P = self.H_inv.shape[0]
+            if self.mode == "sum":
+                self.out = torch.zeros_like(self.H_inv)
+                stream = torch.cuda.current_stream(self.out.device).cuda_stream
+                for k in range(self.K):
+                    dm, dop = self._grads(_C, k, rv)
+                    rc = lib.gsr_fisher_accumulate(P, dm.data_ptr(), dop.data_ptr(),
+                                                   self.weight.data_ptr() + 4 * k, self.out.data_ptr(), stream)
+                    if rc != 0:
+                        raise RuntimeError(f"gsr_fisher_accumulate: {lib.gsr_last_error().decode(errors='replace')}")
+            else:
+                for k in range(self.K):
+                    dm, dop = self._grads(_C, k, rv)
+                    fisher_score(dm, dop, self.H_inv, self.alive, self.workspace, self.out[k:k + 1])
+
+    def _load(self, w2cs):
+        if len(w2cs) > self.K:
+            raise ValueError(f"at most {self.K} poses per launch")
+        with torch.no_grad():
+            self.weight.zero_()
+            for k, w in enumerate(w2cs):
+                self.w2c[k].copy_(w)
+                self.weight[k] = 1.0
+
+    def hessian_sum(self, w2cs, check: bool = True) -> torch.Tensor | None:
+        """sum over the (<= K) poses of H(w2c) over the padded rows [P,4] (one graph launch; dead rows +0).
+        With `check` (one host sync) None when a pose of this launch exceeded the binning capacity."""
+        if self.mode != "sum":
+            raise RuntimeError(f"built for mode='{self.mode}'")
+        self._load(w2cs)
+        if check:
+            self.status.zero_()
+        self.graph.replay()
+        if check and self.overflowed(len(w2cs)):
+            return None
+        return self.out
+
+    def scores(self, w2cs, H_inv, check: bool = True) -> torch.Tensor | None:
+        """gsr_fisher_score of each of the (<= K) poses against H_inv [P,4] (padded rows; the dead ones are not
+        read): float64 [n] (one graph launch); None on a capacity overflow of any of them (`check`)."""
+        if self.mode != "scores":
+            raise RuntimeError(f"built for mode='{self.mode}'")
+        return self._replay_scores(w2cs, H_inv, check)
+
+    def _replay_scores(self, w2cs, H_inv, check):
+        self._load(w2cs)
+        if H_inv is not self.H_inv:  # (a caller may fill self.H_inv in place and pass it)
+            with torch.no_grad():
+                self.H_inv.copy_(H_inv)
+        if check:
+            self.status.zero_()
+        self.graph.replay()
+        if check and self.overflowed(len(w2cs)):
+            return None
+        return self.out[:len(w2cs)].clone()
+
+    def gains(self, w2cs, H_inv, k_sil: float = 1.0, k_eig: float = 1.0, k_sum: float = 1.0, nl_sil: bool = False,
+              nl_eig: bool = False, check: bool = True) -> torch.Tensor | None:
+        """send_gains' (g_sil, g_eig, gain) for each of the (<= K) poses: float64 [n,3] on the device (one graph
+        launch, then combine_gains); None on a capacity overflow (`check`).  The raw counts stay in `counts[:n]`."""
+        if self.mode != "gains":
+            raise RuntimeError(f"built for mode='{self.mode}'")
+        eig = self._replay_scores(w2cs, H_inv, check)
+        if eig is None:
+            return None
+        cam = self.cam
         return combine_gains(self.counts[:len(w2cs)], eig, cam.image_width * cam.image_height, k_sil, k_eig, k_sum,
                              nl_sil, nl_eig)
 
