@@ -7,12 +7,13 @@
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it; the
  * product path (splatam_amd/) never links or calls it.
  *
- * Parity status: the reference CUDA extension cannot be built or run in this
- * container (no nvcc, no NVIDIA GPU) and ships no golden vectors, so kernel
- * numerics are "parity unpinned" against the reference binary.  This
- * restatement follows the .cu sources line by line (citations per function)
- * and is cross-checked in tests/ against torch.autograd through a dense
- * formulation and against finite differences in float64.
+ * Parity status: this restatement follows the .cu sources line by line
+ * (citations per function).  It is cross-checked in tests/ against
+ * torch.autograd through a dense formulation and against finite differences
+ * in float64, and compared with the reference's own kernels compiled by hipcc
+ * for gfx950 (oracle/reference.py; tests/test_gpu_reference.py live on the GPU,
+ * tests/test_reference_goldens_cpu.py on recorded results).  The reference's
+ * nvcc build itself cannot run here.
  *
  * Built twice (see oracle/Makefile):  -DREAL=float  -> oracle/_build/libgsr_oracle_f32.so
  *                                     -DREAL=double -> oracle/_build/libgsr_oracle_f64.so
@@ -28,7 +29,11 @@
  *     (backward.cu:850-1140): the full chain per (pixel, Gaussian) pair and
  *     powf(value, power) applied per pair before summation.  The two vendored
  *     SH bugs (backward.cu:1067 offset M*gid instead of 3*M*gid, and
- *     backward.cu:1117 dropping SH grads when D==0) are NOT replicated.
+ *     backward.cu:1117 dropping SH grads when D==0) are NOT replicated;
+ *   - backward, mode GSR_ORACLE_VENDORED: GSR_ORACLE_FUSED with exactly those two
+ *     bugs replicated: what the reference's binary computes on SH inputs.  It exists
+ *     so that the oracle can be compared with the reference's own kernels on every
+ *     tensor (tests/reference_cases.py); nothing else differs from the fused mode.
  *
  * Threads (OpenMP): preprocess over Gaussians, render / backward over tiles.
  * Results do not depend on the thread count: the backward sums each pair's
@@ -62,6 +67,7 @@ typedef REAL real;
 
 #define GSR_ORACLE_UPSTREAM 0
 #define GSR_ORACLE_FUSED 1
+#define GSR_ORACLE_VENDORED 2
 #define ALPHA_BAND 2e-5
 #define T_BAND 1e-4
 
@@ -501,7 +507,8 @@ typedef struct {
  * Outputs out[]: 0..2 dmean3D, 3..8 dcov3D, 9..11 dscale, 12..15 drot, 16.. dsh (3 per coeff).
  * backward.cu:144-274 (cov2D), 412-475 (cov3D), 480-530 (preprocess), 20-139 (SH). */
 #define NOUT_FIXED 16
-static void chain(const oracle_in* in, const oracle_fwd_out* fo, int g, const real* g2, real fx, real fy, real* out)
+static void chain(const oracle_in* in, const oracle_fwd_out* fo, int g, const real* g2, real fx, real fy, real* out,
+                  int vendored_sh)
 {
     int nsh = in->shs ? (in->D + 1) * (in->D + 1) : 0;
     for (int k = 0; k < NOUT_FIXED + 3 * nsh; k++) out[k] = 0;
@@ -571,7 +578,8 @@ static void chain(const oracle_in* in, const oracle_fwd_out* fo, int g, const re
     out[2] += (pr[8] * mw - pr[11] * mul1) * gx2 + (pr[9] * mw - pr[11] * mul2) * gy2;
     /* --- SH bwd (backward.cu:20-139) --- */
     if (in->shs) {
-        const real* sh = in->shs + (size_t)3 * in->M * g;
+        /* vendored_sh: backward.cu:1067 hands the SH backward shs + M * gid (floats), not 3 * M * gid */
+        const real* sh = in->shs + (size_t)(vendored_sh ? 1 : 3) * in->M * g;
         real dox = m.x - in->campos[0], doy = m.y - in->campos[1], doz = m.z - in->campos[2];
         real len = RSQRT(dox * dox + doy * doy + doz * doz);
         real x = dox / len, y = doy / len, z = doz / len;
@@ -695,6 +703,7 @@ int oracle_backward(const oracle_in* in, const oracle_fwd_out* fo, const real* d
     int gx = (W + BLOCK_X - 1) / BLOCK_X, gy = (H + BLOCK_Y - 1) / BLOCK_Y;
     int nsh = in->shs ? (in->D + 1) * (in->D + 1) : 0;
     if (mode == GSR_ORACLE_UPSTREAM && power != 1) return -1;
+    const int vend = mode == GSR_ORACLE_VENDORED;
     /* zero all outputs (rasterize_points.cu:151-159) */
     memset(go->dmeans2D, 0, sizeof(real) * 3 * (size_t)P);
     memset(go->dcolors, 0, sizeof(real) * 3 * (size_t)P);
@@ -788,7 +797,7 @@ int oracle_backward(const oracle_in* in, const oracle_fwd_out* fo, const real* d
                                 for (int q = 0; q < 9; q++) r[9 + q] += g2[q] < 0 ? -g2[q] : g2[q];
                         } else {
                             /* backward.cu:1040-1137: chain per pair, powf per pair, then sum */
-                            chain(in, fo, g, g2, fx, fy, outbuf);
+                            chain(in, fo, g, g2, fx, fy, outbuf, vend);
                             for (int c = 0; c < 3; c++) r[c] += apply_power(g2[6 + c], power);
                             r[3] += apply_power(g2[0], power);
                             r[4] += apply_power(g2[1], power);
@@ -807,7 +816,7 @@ int oracle_backward(const oracle_in* in, const oracle_fwd_out* fo, const real* d
                                 for (int q = 0; q < 9; q++) {
                                     if (g2[q] == 0) continue;
                                     for (int u = 0; u < 9; u++) e9[u] = u == q ? 1 : 0;
-                                    chain(in, fo, g, e9, fx, fy, col);
+                                    chain(in, fo, g, e9, fx, fy, col, vend);
                                     for (int o2 = 0; o2 < no; o2++) A[o2] += rabs(col[o2]) * rabs(g2[q]);
                                 }
                                 real* s = r + NVS;
@@ -850,7 +859,7 @@ int oracle_backward(const oracle_in* in, const oracle_fwd_out* fo, const real* d
                 go->dmeans2D[3 * g + 1] = a2[1];
                 go->dopacity[g] = a2[5];
                 for (int c = 0; c < 3; c++) go->dcolors[3 * g + c] = a2[6 + c];
-                chain(in, fo, g, a2, fx, fy, outbuf);
+                chain(in, fo, g, a2, fx, fy, outbuf, 0);
                 for (int c = 0; c < 3; c++) go->dmeans3D[3 * g + c] = outbuf[c];
                 for (int c = 0; c < 6; c++) go->dcov3D[6 * g + c] = outbuf[3 + c];
                 if (go->dsh && nsh > 0)
@@ -867,7 +876,7 @@ int oracle_backward(const oracle_in* in, const oracle_fwd_out* fo, const real* d
                     for (int q = 0; q < 9; q++) {
                         if (s2[q] == 0) continue;
                         for (int u = 0; u < 9; u++) e[u] = u == q ? 1 : 0;
-                        chain(in, fo, g, e, fx, fy, col);
+                        chain(in, fo, g, e, fx, fy, col, 0);
                         for (int o2 = 0; o2 < no; o2++) sc[o2] += (col[o2] < 0 ? -col[o2] : col[o2]) * s2[q];
                     }
                     gs->dmeans2D[3 * g] = s2[0];
@@ -897,7 +906,7 @@ int oracle_backward(const oracle_in* in, const oracle_fwd_out* fo, const real* d
             for (int c = 0; c < 3; c++) go->dscales[3 * g + c] = a[14 + c];
             for (int c = 0; c < 4; c++) go->drot[4 * g + c] = a[17 + c];
             go->dopacity[g] = a[21];
-            if (go->dsh && nsh > 0)
+            if (go->dsh && nsh > 0 && !(vend && in->D == 0)) /* backward.cu:1117 adds dL_dsh only if D > 0 */
                 for (int c = 0; c < 3 * nsh; c++) go->dsh[(size_t)3 * in->M * g + c] = a[22 + c];
             if (gs) {
                 const real* s = a + NVS;

@@ -50,6 +50,31 @@ def run_oracle(scene, dL_dcolor=None, *, bg=(0.0, 0.0, 0.0), use_sh=False, use_c
     return fr, grads
 
 
+def run_reference(scene, dL_dcolor=None, *, bg=(0.0, 0.0, 0.0), use_sh=False, use_cov=False, power=1,
+                  scale_modifier=1.0, backward=True):
+    """run_oracle's scene through the reference's own kernels on the GPU (oracle/reference.py; float32,
+    its backward is always the fused one).  Returns (frame, grads) in run_oracle's form."""
+    from . import reference
+    c = scene.cam
+    kw = dict(view=c.viewmatrix.numpy(), proj=c.projmatrix.numpy(), campos=c.campos.numpy(), tanfovx=c.tanfovx,
+              tanfovy=c.tanfovy, H=c.H, W=c.W, bg=np.asarray(bg, np.float32), scale_modifier=scale_modifier)
+    if use_sh:
+        kw.update(shs=scene.shs.numpy(), sh_degree=scene.sh_degree)
+    else:
+        kw.update(colors=scene.colors.numpy())
+    if use_cov:
+        kw.update(cov3D=cov3d_from(scene.scales, scene.rotations, 1.0).numpy())
+    else:
+        kw.update(scales=scene.scales.numpy(), rotations=scene.rotations.numpy())
+    fr = reference.forward(scene.means3D.numpy(), scene.opacities.numpy(), **kw)
+    grads = None
+    if backward:
+        if dL_dcolor is None:
+            dL_dcolor = np.ones((3, c.H, c.W), np.float32)
+        grads = reference.backward(fr, np.asarray(dL_dcolor), power=power)
+    return fr, grads
+
+
 def run_gpu(scene, dL_dcolor=None, *, device="cuda:0", bg=(0.0, 0.0, 0.0), use_sh=False, use_cov=False, power=1,
             scale_modifier=1.0, backward=True, grads_for=None):
     """Runs the product rasterizer (splatam_amd.GaussianRasterizer) and returns numpy results.

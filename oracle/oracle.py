@@ -4,16 +4,19 @@ TEST INFRASTRUCTURE ONLY: imported by ``tests/``, ``__graft_entry__.smoke()`` an
 ``bench.py``'s cpu_baseline leg, never by the product package ``splatam_amd``.
 
 The restatement follows the reference CUDA sources line by line (see the
-header of gsr_oracle.c).  Kernel-level parity is "parity unpinned" against the
-reference binary (it cannot be built or run here); the oracle itself is pinned
-in tests/ by torch.autograd through a dense formulation and by finite
-differences in float64.
+header of gsr_oracle.c).  It is pinned in tests/ by torch.autograd through a dense
+formulation and by finite differences in float64, and against the reference's own
+kernels: oracle/reference.py runs the reference's .cu sources, compiled by hipcc for
+gfx950 (not its nvcc build), and tests/test_gpu_reference.py (live, on the GPU) and
+tests/test_reference_goldens_cpu.py (recorded results, everywhere) compare both builds
+of this oracle with them (DESIGN.md section 4 lists cases and measured bounds).
 """
 from __future__ import annotations
 
 import ctypes
 import os
 import subprocess
+import sys
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -22,11 +25,20 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _BUILD = os.path.join(_HERE, "_build")
 UPSTREAM = 0  # backward.cu:586-748 decomposition (power == 1 only)
 FUSED = 1     # backward.cu:850-1140 per-pair chain with powf(., power)
+VENDORED = 2  # FUSED with the reference's two SH bugs replicated (gsr_oracle.c header): what its binary computes
 
 
 def build() -> None:
-    """Compile both precisions of the oracle (make -C oracle)."""
+    """Compile both precisions of the oracle (make -C oracle), then the reference's own kernels
+    behind oracle/ref_driver.cpp (make -C oracle ref) where a reference checkout is present.
+    The second step never fails the build: without the checkout it does nothing (and keeps an
+    existing oracle/_ref/libref_raster.so); a compiler failure is reported on stderr and leaves
+    reference.available() False, so the tests that need the library skip with that reason."""
     subprocess.run(["make", "-s", "-C", _HERE], check=True)
+    r = subprocess.run(["make", "-s", "-C", _HERE, "ref"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
+                       text=True)
+    if r.returncode != 0:
+        sys.stderr.write("oracle.build: make ref failed (the reference library is optional):\n" + r.stdout[-4000:])
 
 
 _libs: dict = {}
