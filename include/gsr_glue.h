@@ -674,6 +674,38 @@ int gsr_init_frame(int H, int W, const float* gt_im, const float* gt_depth, floa
                    float* logit_opacities, float* log_scales, unsigned char* alive, long long* n_live,
                    unsigned char* overflow, long long* n_added, int* dest, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------ resize --
+ * A frame's copies at other resolutions, for a tracking resolution (the reference's tracking_image_height /
+ * width, scripts/splatam.py:517-523, 588-607: "SplaTAM-S") and a densification resolution of their own: one
+ * launch on `stream` for up to two outputs, nothing read back, no workspace; every input but the sizes is read
+ * on the device when the kernel runs, so the call can be captured in a graph.  Any size ratio, up or down,
+ * separately in x and y.
+ *
+ * Inputs: im [3,H,W], depth [1,H,W].  Output k (k = 0, 1): im_out_k [3,h_k,w_k], depth_out_k [1,h_k,w_k]; an
+ * output whose two pointers are both NULL is skipped (its sizes are not read).  For output pixel (y, x):
+ *   depth: nearest neighbour, the source pixel (floor(y H / h), floor(x W / w)) in integer arithmetic -- the
+ *     rule of cv2.INTER_NEAREST and of torch's mode="nearest".  The value is copied: the same bits.
+ *   colour: bilinear with half-pixel centres and edge clamp, the sample positions of cv2.INTER_LINEAR and of
+ *     torch's F.interpolate(mode="bilinear", align_corners=False), no antialiasing.  Along x: the source
+ *     coordinate is sx = max(0, (x + 0.5) W / w - 0.5), formed exactly from integers: num = (2 x + 1) W - w,
+ *     den = 2 w; num <= 0: x0 = 0, tx = 0; else x0 = num / den (integer quotient), tx = (float)(num - x0 den)
+ *     / (float)den -- two exact conversions (w <= 2^23) and one correctly rounded division, never a float32
+ *     scale factor; x1 = min(x0 + 1, W - 1).  The same in y (y0, y1, ty).  Then, in float32, every operation
+ *     rounded on its own (no contraction), lerp(a, b, t) = a when t == 0, else a + t * (b - a):
+ *         top = lerp(im[c, y0, x0], im[c, y0, x1], tx);   bot = lerp(im[c, y1, x0], im[c, y1, x1], tx);
+ *         out[c, y, x] = lerp(top, bot, ty)
+ *     -- horizontally on the two rows, then vertically.  A tap of weight zero is not read into the result: a
+ *     NaN or an infinity reaches exactly the outputs that one of its four taps enters with a non-zero weight,
+ *     and nothing is masked.  h == H and w == W: every weight is zero and the output is the input's bits.
+ * Difference from the reference, deliberate: its loader resizes the uint8 image (cv2's 11-bit fixed-point
+ * weights, rounded to a byte) and divides by 255 afterwards; this call resizes the float image.  Parity with
+ * cv2's uint8 path is NOT pinned by any test of this repository.
+ * Returns GSR_ERR_INVALID_ARG and launches nothing for H, W < 1 or H * W >= 2^31; a NULL im or depth; an
+ * output with exactly one of its two pointers NULL; a present output with h, w < 1, h * w >= 2^31, or
+ * 2 w W or 2 h H >= 2^31 (the numerators are ints); both outputs absent.  Errors name "resize_frame". */
+int gsr_resize_frame(int H, int W, const float* im, const float* depth, int h0, int w0, float* im_out0,
+                     float* depth_out0, int h1, int w1, float* im_out1, float* depth_out1, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

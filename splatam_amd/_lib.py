@@ -230,6 +230,9 @@ SIGNATURES = {
     "gsr_init_frame": (c_int, [c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_void_p, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    # include/gsr_glue.h: frame resize (H, W, im, depth, then {h, w, im_out, depth_out} twice, stream)
+    "gsr_resize_frame": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                 c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -21,7 +21,7 @@ LIB = os.path.join(HERE, "libgsr.so")
 DIAG = os.path.join(HERE, "_diag")  # experiment / diagnostics libraries that travel to the GPU box
 SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_backward_power.hip", "gsr_capi.hip", "gsr_timing.hip",
            "gsr_glue.hip", "gsr_mapping.hip", "gsr_sh.hip", "gsr_keyframe.hip", "gsr_eval.hip", "gsr_densify.hip",
-           "gsr_viewgain.hip"]
+           "gsr_viewgain.hip", "gsr_resize.hip"]
 ARCH = os.environ.get("GSR_OFFLOAD_ARCH", "gfx950")
 
 

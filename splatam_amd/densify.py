@@ -18,7 +18,8 @@ a sink row).  Here
   two of the six launches); init_literal its comparison form.
 * downscale_capture / downscale_camera give the densification frames of the reference's
   `densification_image_height / width` configurations (scripts/splatam.py:191-215, 558-580, 801-812; the dataset
-  loader's resize: nearest depth, bilinear colour, scaled intrinsics).
+  loader's resize: nearest depth, bilinear colour, scaled intrinsics), for integer factors; splatam_amd.resize
+  has the one-launch form for any ratio (gsr_resize_frame).
 
 log_scales is the one output that is not pinned bitwise between the two forms (the device library's logf against
 torch.log); everything else is.

@@ -23,8 +23,15 @@ Densification has two forms (`densify_mode`): "torch" (the default), densify_sta
 the silhouette render followed by splatam_amd.densify.densify_device (gsr_densify_frame: the median by
 selection, the ranks and the new rows in six launches; only selected pixels write).  With densify_frames /
 densify_cam / densify_intrinsics either form renders and reads a densification frame of its own resolution
-(the reference's densification_image_height / width, scripts/splatam.py:801-812); tracking, mapping and the
-keyframe bank keep the full-resolution frames.
+(the reference's densification_image_height / width, scripts/splatam.py:801-812).  With track_frames / track_cam
+the tracker renders and compares against a tracking frame of its own resolution (the reference's
+tracking_image_height / width, scripts/splatam.py:517-523, 588-607, 680-687 -- what makes
+configs/replica/splatam_s.py "SplaTAM-S"): only the tracker's slot holds it; densification, the keyframe dicts
+and bank, mapping, evaluate() and the view scorer keep the full-resolution frames, as in the reference, where
+only tracking_curr_data differs.  track_size / densify_size (h, w) have the sequence make those frames itself:
+the cameras and intrinsics through splatam_amd.resize (resized_camera, scale_intrinsics), each frame's small
+copies by one gsr_resize_frame launch (resize.resize_device) -- at construction for the frames given, in push()
+for a frame that arrives, so the realtime loop's caller pushes the full frame and nothing else.
 
 Two keyframe policies (`keyframe_policy`):
 * "window" (the default): the last `window - 1` keyframes plus the current frame; frame 0 and every
@@ -43,7 +50,9 @@ Two keyframe policies (`keyframe_policy`):
 
 track_cfg.use_depth_loss_thres (the reference's iPhone and ScanNet++ configurations; scripts/splatam.py:745-758):
 a frame whose last tracking iteration's depth loss is not below track_cfg.depth_loss_thres tracks for
-tracking_iters more iterations, once.  Both loops then build their trackers with loss_terms=True and pass the
+tracking_iters more iterations, once.  The depth loss is a sum over the TRACKING frame's pixels (as in the reference,
+whose loss is formed on tracking_curr_data), so with a tracking resolution the threshold is resolution-dependent:
+a quarter of the pixels give about a quarter of the sum.  Both loops then build their trackers with loss_terms=True and pass the
 threshold to GraphTracker.track_frame, which reads that one float per tracked frame -- the only host read of
 frame(), and only with the option on (the reference reads the loss in every iteration).  tracking_iters_run
 lists, per frame() call, the tracking iterations run (0 for frame 0, which is not tracked): an entry of
@@ -73,6 +82,7 @@ from .densify import make_workspace as make_densify_workspace
 from .keyframes import KeyframeBank, WordFeed, draw_words, make_workspace, pose_w2c, select_device, \
     select_literal, words_tensor
 from .mapper import GAUSS_KEYS, GraphMapper
+from .resize import check_track_args, resize_device, resized_camera, scale_intrinsics
 from .slam import MappingConfig, TrackingConfig, build_rotation, color_key, matrix_to_quaternion, \
     transform_to_frame, transformed_params2depthplussilhouette
 from .tracker import GraphTracker
@@ -324,7 +334,8 @@ class _SequenceBase:
     OPTIONS = ("frames", "cam", "w2c", "intrinsics", "bin_capacity", "tracking_iters", "mapping_iters", "track_replay",
                "window", "keyframe_every", "sil_thres", "track_cfg", "map_cfg", "prune", "scene_radius",
                "keyframe_policy", "overlap_pixels", "densify_mode", "densify_frames", "densify_cam",
-               "densify_intrinsics", "median_thr", "median_scale", "num_frames", "map_every")
+               "densify_intrinsics", "median_thr", "median_scale", "num_frames", "map_every", "track_frames",
+               "track_cam", "track_size", "densify_size")
 
     def _set_options(self, args: dict):
         """Stores the constructor arguments both classes take (OPTIONS, out of the constructor's locals()) as
@@ -338,11 +349,52 @@ class _SequenceBase:
             raise ValueError("map_every >= 1")
         check_densify_args(self.densify_mode, self.densify_frames, self.densify_cam, self.densify_intrinsics,
                            self.frames)
+        check_track_args(self.track_frames, self.track_cam, self.frames)
+        self._set_sizes()
         self.overlap_pixels = int(self.overlap_pixels)
         if self.scene_radius is None:  # initialize_first_timestep: max depth / scene_radius_depth_ratio (3, the config's)
             self.scene_radius = self.frames[0]["depth"].max() / 3.0
         self.keyframes = [self._kf(0)]
         self.tracking_iters_run = []  # per frame() call: the tracking iterations run (0: frame 0, not tracked)
+
+    def _set_sizes(self):
+        """track_size / densify_size (h, w): the sequence makes the small frames itself -- the camera (and the
+        densification intrinsics) through splatam_amd.resize, the frames given so far by one gsr_resize_frame
+        launch each (_make_small).  Exclusive with track_frames / densify_frames."""
+        if self.track_size is not None and self.track_frames is not None:
+            raise ValueError("track_size: exclusive with track_frames / track_cam")
+        if self.densify_size is not None and self.densify_frames is not None:
+            raise ValueError("densify_size: exclusive with densify_frames / densify_cam / densify_intrinsics")
+        if self.track_size is None and self.densify_size is None:
+            return
+        d0 = self.frames[0]["depth"]
+        H, W, dev = int(d0.shape[-2]), int(d0.shape[-1]), d0.device
+        w2c = None if self.w2c is None else self.w2c.detach().cpu()
+        if self.track_size is not None:
+            self.track_size = tuple(int(v) for v in self.track_size)
+            self.track_cam = resized_camera(W, H, self.intrinsics, *self.track_size, dev, w2c=w2c)
+            self.track_frames = []
+        if self.densify_size is not None:
+            self.densify_size = tuple(int(v) for v in self.densify_size)
+            self.densify_cam = resized_camera(W, H, self.intrinsics, *self.densify_size, dev, w2c=w2c)
+            self.densify_intrinsics = scale_intrinsics(self.intrinsics, H, W, *self.densify_size)
+            self.densify_frames = []
+        for f in self.frames:
+            tf, df = self._make_small(f)
+            if tf is not None:
+                self.track_frames.append(tf)
+            if df is not None:
+                self.densify_frames.append(df)
+
+    def _make_small(self, frame: dict) -> tuple:
+        """(tracking frame, densification frame) of a full frame under track_size / densify_size (None where
+        the size is not set): one gsr_resize_frame launch for both, nothing read back."""
+        ts, ds = self.track_size, self.densify_size
+        if ts is not None and ds is not None:
+            return resize_device(frame, ts, ds)
+        if ts is not None:
+            return resize_device(frame, ts), None
+        return None, (resize_device(frame, ds) if ds is not None else None)
 
     def _depth_loss_thres(self):
         """GraphTracker.track_frame's depth_loss_thres: the configured threshold, or None (option off)."""
@@ -357,21 +409,39 @@ class _SequenceBase:
         """Whether frame t densifies and maps (map_every, scripts/splatam_realtime.py:844): frame 0 always."""
         return t == 0 or (t + 1) % int(self.map_every) == 0
 
-    def _append_frame(self, im: torch.Tensor, depth: torch.Tensor, densify_frame=None) -> int:
-        """A frame that arrived: appended to the frame list (and its densification frame to densify_frames, when
-        the capture has those).  Returns its index; ValueError beyond num_frames (the pose columns)."""
+    def _append_frame(self, im: torch.Tensor, depth: torch.Tensor, densify_frame=None, track_frame=None) -> int:
+        """A frame that arrived: appended to the frame list (and its densification frame to densify_frames, its
+        tracking frame to track_frames, when the capture has those; under densify_size / track_size the sequence
+        makes them here, _make_small, and takes none).  Returns its index; ValueError beyond num_frames (the
+        pose columns)."""
         t = len(self.frames)
         if self.num_frames is None or t >= int(self.num_frames):
             raise ValueError(f"frame {t}: the sequence holds num_frames = {self.num_frames} frames")
-        if (densify_frame is None) != (self.densify_frames is None):
+        if (densify_frame is not None and self.densify_size is not None) or \
+                (track_frame is not None and self.track_size is not None):
+            raise ValueError("densify_size / track_size: the sequence makes that frame itself")
+        if self.densify_size is None and (densify_frame is None) != (self.densify_frames is None):
             raise ValueError("densify_frame: one per frame when the capture has densify_frames, else none")
+        if self.track_size is None and (track_frame is None) != (self.track_frames is None):
+            raise ValueError("track_frame: one per frame when the capture has track_frames, else none")
+        made_t, made_d = self._make_small({"im": im, "depth": depth})
+        track_frame = made_t if track_frame is None else track_frame
+        densify_frame = made_d if densify_frame is None else densify_frame
         self.frames.append({"im": im, "depth": depth})
         if densify_frame is not None:
             self.densify_frames.append(densify_frame)
+        if track_frame is not None:
+            self.track_frames.append(track_frame)
         return t
 
     def _kf(self, t: int) -> dict:
         return {"cam": self.cam, "w2c": self.w2c, "im": self.frames[t]["im"], "depth": self.frames[t]["depth"], "id": t}
+
+    def _track_curr(self, t: int) -> dict:
+        """What the tracker renders and compares against for frame t: the frame itself, or the tracking
+        resolution's (track_frames / track_cam, scripts/splatam.py:588-607, 680-687); w2c stays the first frame's."""
+        f, cam = (self.frames[t], self.cam) if self.track_frames is None else (self.track_frames[t], self.track_cam)
+        return {"cam": cam, "w2c": self.w2c, "im": f["im"], "depth": f["depth"]}
 
     def _densify_kf(self, t: int) -> tuple[dict, tuple]:
         """The frame densification reads and its intrinsics: the tracking frame, or the densification
@@ -405,7 +475,10 @@ class SlamSequence(_SequenceBase):
     params: the initial map (SplaTAM's init from frame 0; isotropic, rgb colours) with one pose column per frame;
     frames: per frame {"im", "depth"} targets (all sharing `cam` / `w2c`, the first frame's, like the reference);
     intrinsics (fx, fy, cx, cy).  frame(t) runs one frame; run(frames) a range of them; push(im, depth) one that
-    arrives (num_frames given).  params None: the map is init_map_device's, from frames[0]."""
+    arrives (num_frames given).  params None: the map is init_map_device's, from frames[0].
+    track_frames / track_cam: the tracker's frames and camera at a resolution of their own (everything else
+    keeps `frames`); track_size / densify_size (h, w): the sequence makes the tracking / densification frames
+    and cameras itself (splatam_amd.resize)."""
 
     def __init__(self, params: dict, frames: list, cam, w2c, intrinsics, capacity: int, bin_capacity: int,
                  tracking_iters: int = 40, mapping_iters: int = 60, track_replay: int = 20, window: int = 8,
@@ -413,7 +486,8 @@ class SlamSequence(_SequenceBase):
                  map_cfg: MappingConfig = MappingConfig(), prune: bool | None = None, seed: int = 0,
                  scene_radius=None, keyframe_policy: str = "window", overlap_pixels: int = 1600,
                  densify_mode: str = "torch", densify_frames=None, densify_cam=None, densify_intrinsics=None,
-                 median_thr=None, median_scale: float = 50.0, num_frames: int | None = None, map_every: int = 1):
+                 median_thr=None, median_scale: float = 50.0, num_frames: int | None = None, map_every: int = 1,
+                 track_frames=None, track_cam=None, track_size=None, densify_size=None):
         if params is not None and (color_key(params) != "rgb_colors" or params["log_scales"].shape[1] != 1):
             raise ValueError("SlamSequence: SplaTAM's isotropic rgb map (the tracking fast path's form)")
         if tracking_iters % track_replay:
@@ -432,7 +506,7 @@ class SlamSequence(_SequenceBase):
         self.overflow = torch.zeros(1, dtype=torch.bool, device=dev)
         self.dstatus = torch.zeros(4, dtype=torch.int32, device=dev)
         if densify_mode == "device":
-            d0 = (densify_frames if densify_frames is not None else frames)[0]["depth"]
+            d0 = (self.densify_frames if self.densify_frames is not None else frames)[0]["depth"]
             self.densify_workspace = make_densify_workspace(d0.shape[-2], d0.shape[-1], dev)
         padded = None
         if params is None:  # the map is born from frame 0 (initialize_first_timestep), on the device
@@ -458,8 +532,8 @@ class SlamSequence(_SequenceBase):
         self.slot = {k: (v.detach() if k in GAUSS_KEYS + ("rgb_colors",) else v) for k, v in self.params.items()}
         self.slot["cam_unnorm_rots"] = q[..., :1].detach().clone().requires_grad_(True)
         self.slot["cam_trans"] = tr[..., :1].detach().clone().requires_grad_(True)
-        f0 = self.frames[0]
-        self.slot_curr = {"cam": self.cam, "w2c": self.w2c, "im": f0["im"].clone(), "depth": f0["depth"].clone()}
+        c0 = self._track_curr(0)  # (the tracking resolution's frame and camera, when the capture has those)
+        self.slot_curr = dict(c0, im=c0["im"].clone(), depth=c0["depth"].clone())
         self.tracker = GraphTracker(self.slot, self.slot_curr, 0, iters_per_graph=self.track_replay,
                                     cfg=self.track_cfg, warmup_iters=1, fuse_pose=True, alive=self.alive,
                                     capacity=self.bin_capacity, loss_terms=self.track_cfg.use_depth_loss_thres)
@@ -491,8 +565,9 @@ class SlamSequence(_SequenceBase):
         with torch.no_grad():
             self.slot["cam_unnorm_rots"][..., 0] = p["cam_unnorm_rots"][..., t]
             self.slot["cam_trans"][..., 0] = p["cam_trans"][..., t]
-            self.slot_curr["im"].copy_(self.frames[t]["im"])
-            self.slot_curr["depth"].copy_(self.frames[t]["depth"])
+            curr = self._track_curr(t)
+            self.slot_curr["im"].copy_(curr["im"])
+            self.slot_curr["depth"].copy_(curr["depth"])
         ran = self.tracker.track_frame(self.tracking_iters, check=False, depth_loss_thres=self._depth_loss_thres())
         with torch.no_grad():
             p["cam_unnorm_rots"][..., t] = self.slot["cam_unnorm_rots"][..., 0]
@@ -594,8 +669,15 @@ class SlamSequence(_SequenceBase):
         run as frame t = len(frames) - 1, with its pose when `w2c` is given (frame()).  Needs num_frames: the
         pose tensors have that many columns, and a frame beyond them raises ValueError.  densify_frame
         {"im", "depth"}: the frame at the densification resolution, for a capture with densify_frames.
-        Returns t.  Nothing is read back (but see track_cfg.use_depth_loss_thres)."""
-        t = self._append_frame(im, depth, densify_frame)
+        Under densify_size / track_size the sequence makes the small frames itself (one gsr_resize_frame
+        launch) and the caller pushes the full frame alone.  A capture with track_frames goes through
+        push_frames.  Returns t.  Nothing is read back (but see track_cfg.use_depth_loss_thres)."""
+        return self.push_frames(im, depth, w2c=w2c, densify_frame=densify_frame)
+
+    def push_frames(self, im: torch.Tensor, depth: torch.Tensor, w2c=None, densify_frame=None, track_frame=None) -> int:
+        """push() with the frame at the tracking resolution: track_frame {"im", "depth"}, for a capture with
+        track_frames (one per frame, by the rule of densify_frame)."""
+        t = self._append_frame(im, depth, densify_frame, track_frame)
         self.frame(t, w2c=w2c)
         return t
 
@@ -759,7 +841,8 @@ class PerFrameSlam(_SequenceBase):
                  map_cfg: MappingConfig = MappingConfig(), prune: bool | None = None, scene_radius=None,
                  bin_capacity: int | None = None, keyframe_policy: str = "window", overlap_pixels: int = 1600,
                  densify_mode: str = "torch", densify_frames=None, densify_cam=None, densify_intrinsics=None,
-                 median_thr=None, median_scale: float = 50.0, num_frames: int | None = None, map_every: int = 1):
+                 median_thr=None, median_scale: float = 50.0, num_frames: int | None = None, map_every: int = 1,
+                 track_frames=None, track_cam=None, track_size=None, densify_size=None):
         self._set_options(locals())
         self.kf_list = []  # "overlap": the keyframes in the order appended, each with its est_w2c snapshot
         self.windows = []  # "overlap": per frame, the selected window's time indices
@@ -775,8 +858,7 @@ class PerFrameSlam(_SequenceBase):
             tp = dict(p)
             tp["cam_unnorm_rots"] = p["cam_unnorm_rots"][..., t:t + 1].clone().requires_grad_(True)
             tp["cam_trans"] = p["cam_trans"][..., t:t + 1].clone().requires_grad_(True)
-            curr = {"cam": self.cam, "w2c": self.w2c, "im": self.frames[t]["im"], "depth": self.frames[t]["depth"]}
-            tracker = GraphTracker(tp, curr, 0, iters_per_graph=self.track_replay, cfg=self.track_cfg, warmup_iters=1,
+            tracker = GraphTracker(tp, self._track_curr(t), 0, iters_per_graph=self.track_replay, cfg=self.track_cfg, warmup_iters=1,
                                    fuse_pose=True, capacity=self.bin_capacity,
                                    loss_terms=self.track_cfg.use_depth_loss_thres)
             ran = tracker.track_frame(self.tracking_iters, depth_loss_thres=self._depth_loss_thres())
