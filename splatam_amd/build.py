@@ -19,7 +19,10 @@ OBJDIR = os.path.join(HERE, "_build")
 INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(HERE, "libgsr.so")
 DIAG = os.path.join(HERE, "_diag")  # experiment / diagnostics libraries that travel to the GPU box
-SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_backward_power.hip", "gsr_capi.hip", "gsr_timing.hip",
+# The forward's stage files: one translation unit, gsr_forward_unit.hip, includes them in this order (one code
+# object for the kernels that run back to back in a step; the file says why).  Each also compiles on its own.
+FORWARD_STAGES = ["gsr_preprocess.hip", "gsr_binning.hip", "gsr_radix.hip", "gsr_forward.hip", "gsr_reuse.hip"]
+SOURCES = ["gsr_forward_unit.hip", "gsr_backward.hip", "gsr_backward_power.hip", "gsr_capi.hip", "gsr_timing.hip",
            "gsr_glue.hip", "gsr_mapping.hip", "gsr_sh.hip", "gsr_keyframe.hip", "gsr_eval.hip", "gsr_densify.hip",
            "gsr_viewgain.hip", "gsr_resize.hip"]
 ARCH = os.environ.get("GSR_OFFLOAD_ARCH", "gfx950")
@@ -44,6 +47,8 @@ def _compile(src: str, objdir: str = OBJDIR, extra=(), csrc: str = CSRC, include
     obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
     srcp = os.path.join(csrc, src)
     deps = [srcp, os.path.join(include, "gsr.h"), os.path.join(include, "gsr_glue.h")] + [os.path.join(csrc, h) for h in os.listdir(csrc) if h.endswith(".h")]
+    if src == "gsr_forward_unit.hip":  # (the files it includes; a revision before the unit has none)
+        deps += [os.path.join(csrc, s) for s in FORWARD_STAGES if os.path.exists(os.path.join(csrc, s))]
     if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(d) for d in deps):
         return obj
     cmd = [hipcc(), *flags(csrc, include), *extra, "-c", srcp, "-o", obj]
@@ -53,11 +58,11 @@ def _compile(src: str, objdir: str = OBJDIR, extra=(), csrc: str = CSRC, include
     return obj
 
 
-def _compile_all(objdir: str, extra=(), csrc: str = CSRC, include: str = INCLUDE):
-    """Every translation unit of SOURCES compiled into `objdir` (stale objects only); the object paths."""
+def _compile_all(objdir: str, extra=(), csrc: str = CSRC, include: str = INCLUDE, sources=SOURCES):
+    """Every translation unit of `sources` compiled into `objdir` (stale objects only); the object paths."""
     os.makedirs(objdir, exist_ok=True)
-    with ThreadPoolExecutor(max_workers=min(16, len(SOURCES))) as ex:
-        return list(ex.map(lambda s: _compile(s, objdir, extra, csrc, include), SOURCES))
+    with ThreadPoolExecutor(max_workers=min(16, len(sources))) as ex:
+        return list(ex.map(lambda s: _compile(s, objdir, extra, csrc, include), sources))
 
 
 def _link(objs, lib: str) -> str:
@@ -153,6 +158,19 @@ def export_rev(rev: str, work: str):
     return os.path.join(work, "splatam_amd", "csrc"), os.path.join(work, "include")
 
 
+def rev_sources(rev: str):
+    """The translation units of git revision `rev`: the SOURCES list of its own build.py (a list literal), which
+    need not be this tree's."""
+    import ast
+    r = subprocess.run(["git", "-C", ROOT, "show", f"{rev}:splatam_amd/build.py"], capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"git show {rev}:splatam_amd/build.py failed: {r.stderr}")
+    for node in ast.parse(r.stdout).body:
+        if isinstance(node, ast.Assign) and any(getattr(t, "id", None) == "SOURCES" for t in node.targets):
+            return ast.literal_eval(node.value)
+    raise RuntimeError(f"no SOURCES list in {rev}:splatam_amd/build.py")
+
+
 def build_from_rev(rev: str, tag: str) -> str:
     """A/B baseline without macros in the sources: libgsr built from the csrc/ and include/ trees of git
     revision `rev` (exported to a scratch directory) into splatam_amd/_diag/libgsr_<tag>.so, which
@@ -162,7 +180,7 @@ def build_from_rev(rev: str, tag: str) -> str:
     try:
         csrc, inc = export_rev(rev, work)
         os.makedirs(DIAG, exist_ok=True)
-        return _link(_compile_all(work, (), csrc, inc), os.path.join(DIAG, f"libgsr_{tag}.so"))
+        return _link(_compile_all(work, (), csrc, inc, rev_sources(rev)), os.path.join(DIAG, f"libgsr_{tag}.so"))
     finally:
         shutil.rmtree(work, ignore_errors=True)
 

@@ -22,6 +22,7 @@
 #include "gsr_chain.h"
 #include "gsr_clock.h"
 #include "gsr_diag.h"
+#include "gsr_dispatch.h"
 #include "gsr_glue_common.h"
 #include "gsr_launch.h"
 #include "gsr_layout.h"
@@ -127,14 +128,6 @@ hipError_t launch_render_track(const Camera& cam, const uint2* ranges, uint64_t*
                        keys, geo.rr, geo.blocksums, final_T, n_contrib, out_color, out_color2, out_depth, guard, clk,
                        l1, inst);
     return hipGetLastError();
-}
-
-// Run-time booleans into template arguments: f.template operator()<B...>() with B the given values, in order.
-template <bool... B, class F>
-static auto dispatch_bools(F f) { return f.template operator()<B...>(); }
-template <bool... B, class F, class... R>
-static auto dispatch_bools(F f, bool b, R... rest) {
-    return b ? dispatch_bools<B..., true>(f, rest...) : dispatch_bools<B..., false>(f, rest...);
 }
 
 // (need, dual) decoded into the optional per-pair sums of the variant: opacity, colours, second colours and

@@ -6,29 +6,30 @@
 
 namespace gsr {
 
-// ------------------------------------------------------- gsr_forward.hip --
+// ---------------------------------------------------- gsr_preprocess.hip --
 hipError_t launch_preprocess(const Camera& cam, const GaussIn& g, GeomPtrs geo, int* radii, uint32_t* counts,
                              bool lds_hist, int ntiles, int nb, hipStream_t s, unsigned long long* clk = nullptr);
+hipError_t launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* vis, hipStream_t s);
+// ------------------------------------------------------- gsr_binning.hip --
 hipError_t launch_tile_colscan(uint32_t* counts, int nb, int ntiles, uint32_t* tot, GeomPtrs geo, uint2* ranges,
                                uint32_t* status, bool tail, hipStream_t s, unsigned long long* clk = nullptr,
                                Gate gate = Gate{});
-hipError_t launch_exclusive_scan(uint32_t* data, uint32_t n, uint32_t* total, hipStream_t s);
 hipError_t launch_scan_counts(GeomPtrs geo, int nb, const uint32_t* tile_count, int tile_stride, int ntiles,
                               uint2* ranges, uint32_t* status, hipStream_t s);
-hipError_t launch_duplicate(const Camera& cam, int P, GeomPtrs geo, uint64_t* keys, uint32_t* gid,
-                            int nb, hipStream_t s);
-// lds_hist: the colscan ran without its scan tail; every workgroup scans the
-// workgroup and tile totals (`tot`) itself, workgroup 0 writes ranges,
-// counters and `status` (static mode; may be null).
 // Row-major render schedule (the paths that do not run tile_plan).
 hipError_t launch_identity_order(uint32_t* order, int ntiles, hipStream_t s);
+// lds_hist: the colscan ran without its scan tail; every workgroup scans the workgroup and tile totals (`tot`)
+// itself, workgroup 0 writes ranges, counters and `status` (static mode; may be null).
 hipError_t launch_duplicate_bucket(const Camera& cam, int P, GeomPtrs geo, uint2* ranges, const uint32_t* tot,
                                    uint32_t* cursor, bool lds_hist, int ntiles, uint64_t* keys, uint64_t* point_list,
                                    int nb, SpecGuard guard, uint32_t* status, hipStream_t s, unsigned long long* clk = nullptr);
+// --------------------------------------------------------- gsr_radix.hip --
+hipError_t launch_duplicate(const Camera& cam, int P, GeomPtrs geo, uint64_t* keys, uint32_t* gid,
+                            int nb, hipStream_t s);
 hipError_t launch_radix_sort(uint64_t* keys[2], uint32_t* vals[2], uint32_t* hist, uint32_t n, int nsb, int npass,
                              hipStream_t s);
-hipError_t launch_gather_ids(const uint32_t* vals, const uint32_t* gid, uint64_t* point_list, uint32_t n,
-                             hipStream_t s);
+hipError_t launch_gather_ids(const uint32_t* vals, const uint32_t* gid, uint64_t* point_list, uint32_t n, hipStream_t s);
+// ------------------------------------------------------- gsr_forward.hip --
 // SplaTAM's tracking L1 loss (get_loss tracking=True, scripts/splatam.py:262-296) and its
 // gradient images formed in the dual forward's per-pixel epilogue (gsr_track_forward_dual_static):
 // the same mask / sums / sign gradient as gsr_track_l1_fwd_bwd, without reading the images back.
@@ -47,26 +48,25 @@ int track_l1_fused_scratch_floats(int ntiles);
 // keys: the unsorted tile buckets (render_fwd sorts each tile's bucket into point_list in
 // its prologue; the keys are scratch afterwards); nullptr when point_list is already
 // sorted (radix fallback)
-hipError_t launch_render_fwd(const Camera& cam, const uint2* ranges, uint64_t* point_list,
-                             uint64_t* keys, GeomPtrs geo,
-                             const float* colors2, float* final_T, uint32_t* n_contrib, float* out_color,
-                             float* out_color2, float* out_depth, SpecGuard guard, hipStream_t s,
+hipError_t launch_render_fwd(const Camera& cam, const uint2* ranges, uint64_t* point_list, uint64_t* keys,
+                             GeomPtrs geo, const float* colors2, float* final_T, uint32_t* n_contrib,
+                             float* out_color, float* out_color2, float* out_depth, SpecGuard guard, hipStream_t s,
                              unsigned long long* clk = nullptr, const TrackL1* l1 = nullptr);
-hipError_t launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* vis, hipStream_t s);
+// --------------------------------------------------------- gsr_reuse.hip --
 // geometry reuse (gsr_forward_reuse): the render records' colours replaced by `colors` [P,3]
 hipError_t launch_recolour(int P, const float* colors, GeomPtrs geo, hipStream_t s, Gate gate = Gate{});
 // gated geometry reuse: geom [0, counters) + counters[0..3] and the radii from the previous call, the render
 // records' colour quarter replaced by this call's colours (recolour fused into the copy)
 hipError_t launch_reuse_copy(Gate gate, const void* prev_geom, void* geom, size_t geom_bytes, size_t tiles_offset,
                              const float* colors, const int* prev_radii, int* radii, int P, hipStream_t s);
-// *word = e when any pair differs bitwise (word not cleared: see Gate)
-hipError_t launch_epoch_mismatch(const struct EqualPairs& q, uint32_t* word, uint32_t e, hipStream_t s);
 struct EqualPairs {
     int npairs;
     const float* a[8];
     const float* b[8];
     long long n[8];
 };
+// *word = e when any pair differs bitwise (word not cleared: see Gate)
+hipError_t launch_epoch_mismatch(const EqualPairs& q, uint32_t* word, uint32_t e, hipStream_t s);
 hipError_t launch_bitwise_equal(const EqualPairs& q, int* flag, hipStream_t s);
 // ------------------------------------------------------ gsr_backward.hip --
 // (the tile backward its render kernels inline, bwd_tile, and render_bwd_kernel itself: gsr_render_bwd.h)

@@ -1,5 +1,6 @@
 // gsr_render_fwd.h -- the tile forward of render_fwd_kernel as a device function (fwd_tile), with the
-// per-tile sort it starts with: shared by render_fwd_kernel (gsr_forward.hip) and the tracking kernel
+// per-tile sort it starts with (its input: the tile buckets of gsr_binning.hip; the pipeline's map is at the
+// top of gsr_forward.hip): shared by render_fwd_kernel (gsr_forward.hip) and the tracking kernel
 // that runs a tile's forward and backward in one workgroup (render_track_kernel, gsr_backward.hip; the tile
 // backward is gsr_render_bwd.h).
 #pragma once

@@ -1,4 +1,4 @@
-"""The render schedule (tile_plan in the bucketed duplicate, gsr_forward.hip): render workgroup i renders tile
+"""The render schedule (tile_plan in the bucketed duplicate, gsr_binning.hip): render workgroup i renders tile
 order[i].  It must be a permutation of the tiles (every tile rendered once -- the rasterized images of every
 parity test depend on it only through that), and it deals the tiles so that the CUs rendering one tile fewer
 (slots s with s mod ncu >= ntiles mod ncu) take the longest lists: with lengths bucketed by 4 (the counting

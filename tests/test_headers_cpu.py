@@ -5,11 +5,13 @@ gsr_common.h, which the headers were cut from, is gone; the files that launch no
 gsr_launch.h (read from the preprocessor's dependency output, not from the source text); and adam_coef
 (csrc/gsr_adam.h), called from a stand-alone host program, returns bit for bit the five floats the three fills
 it replaced computed; and rec_sums (csrc/gsr_launch.h), likewise from a host program, gives the instance record
-layouts the three statements it replaced gave.
+layouts the three statements it replaced gave.  Two tests read the source text alone (no hipcc): gsr_launch.h's
+file banners name the file that defines each launcher below them, and every declared launcher has a caller.
 """
 import glob
 import math
 import os
+import re
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
@@ -54,6 +56,58 @@ def test_does_not_reach_the_launchers(hipcc, name):
     deps = {os.path.basename(d) for d in r.stdout.replace("\\\n", " ").split()}
     assert "gsr_layout.h" in deps or "gsr_wave.h" in deps, deps  # (the output does list the csrc headers)
     assert "gsr_launch.h" not in deps
+
+
+_BANNER = re.compile(r"^// -+ (gsr_\w+\.hip) --$")
+_LAUNCHER = re.compile(r"^hipError_t (launch_\w+)\(")
+
+
+def _declared_launchers():
+    """[(launcher, the file whose banner it stands under)] of gsr_launch.h, in order."""
+    out, home = [], None
+    for ln in open(os.path.join(CSRC, "gsr_launch.h")).read().splitlines():
+        if m := _BANNER.match(ln):
+            home = m.group(1)
+        elif m := _LAUNCHER.match(ln):
+            out.append((m.group(1), home))
+    return out
+
+
+def _defined_launchers(path):
+    """The launchers a source defines: a definition starts its line with the return type, a call does not."""
+    return {m.group(1) for ln in open(path).read().splitlines() if (m := _LAUNCHER.match(ln))}
+
+
+def test_launch_header_names_each_launchers_file():
+    """gsr_launch.h groups its declarations under one banner per defining file: every launch_* declared under a
+    banner is defined in the file the banner names, and every named file is compiled: a translation unit of
+    build.SOURCES, or one of build.FORWARD_STAGES, which the unit gsr_forward_unit.hip (in SOURCES) includes, all
+    of them and nothing else, in that order.
+    Works on the source text (no compiler): cheap, and the banners are comments, which only text can check."""
+    decl = _declared_launchers()
+    assert len(decl) >= 30 and all(home for _, home in decl), decl
+    files = sorted({home for _, home in decl})
+    unit = open(os.path.join(CSRC, "gsr_forward_unit.hip")).read()
+    code = [ln for ln in unit.splitlines() if ln.strip() and not ln.startswith("//")]
+    assert "gsr_forward_unit.hip" in build.SOURCES and code == [f'#include "{s}"' for s in build.FORWARD_STAGES], code
+    compiled = set(build.SOURCES) | set(build.FORWARD_STAGES)
+    assert set(files) <= compiled, sorted(set(files) - compiled)
+    defined = {f: _defined_launchers(os.path.join(CSRC, f)) for f in files}
+    misplaced = [(name, home) for name, home in decl if name not in defined[home]]
+    assert not misplaced, misplaced
+
+
+def test_no_launcher_is_dead():
+    """Every launch_* that gsr_launch.h declares occurs, as a whole word, somewhere in csrc/*.hip or *.cpp other
+    than on the line that defines it and outside `//` comments (the sources have no block comments naming a
+    launcher): a launcher nobody calls (and its kernel) is deleted, not kept.  Source text only, like the test
+    above."""
+    lines = [ln.split("//")[0]
+             for p in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp")))
+             for ln in open(p).read().splitlines()]
+    dead = [name for name, _ in _declared_launchers()
+            if not any(re.search(rf"\b{name}\b", ln) for ln in lines if not ln.startswith(f"hipError_t {name}("))]
+    assert not dead, dead
 
 
 LAYOUT_MAIN = r"""
