@@ -706,6 +706,44 @@ int gsr_init_frame(int H, int W, const float* gt_im, const float* gt_depth, floa
 int gsr_resize_frame(int H, int W, const float* im, const float* depth, int h0, int w0, float* im_out0,
                      float* depth_out0, int h1, int w1, float* im_out1, float* depth_out1, void* stream);
 
+/* ------------------------------------------------------------------ ingest --
+ * A raw sensor frame into the float frame the sequence reads and, in the same launch, into its copies at up to
+ * two other resolutions: what the reference's intake does op by op on arrival (scripts/ros_handler.py:402-411,
+ * 434-435; datasets/gradslam_datasets/basedataset.py:250-257, 312-316).  One launch on `stream`, nothing read
+ * back, no workspace; every input but the sizes and the scalars is read on the device when the kernel runs, so
+ * the call can be captured in a graph.
+ *
+ * Inputs: rgb_hwc, the interleaved uint8 image [H,W,3], at ANY byte address; depth_u16, the uint16 depth image
+ * [H,W] in sensor units, at any 2-byte address (a frame may be a slice of a larger capture buffer).  Outputs:
+ * im [3,H,W], depth [1,H,W] (float32, 4-byte aligned; 16-byte aligned pointers with H W % 4 == 0 get vector
+ * stores) and the small outputs k = 0, 1 as in gsr_resize_frame.  Three roundings are the whole contract:
+ *   colour: im[c, y, x] = (float)rgb[y, x, c] / 255.0f -- ONE correctly rounded float32 division, not a
+ *     multiply by a reciprocal.  The value depends on the byte alone (a 256-entry table states it).  torch's
+ *     device-side `x / 255` multiplies by the rounded reciprocal and may differ from this by one ulp for some
+ *     bytes; torch's CPU form (a true division) does not differ.
+ *   depth: d = (float)((double)u / png_depth_scale) -- the float64 quotient of numpy's `arr / png_depth_scale`,
+ *     rounded to float32 ONCE.  A correctly rounded float32 division (float)u / (float)scale gives the same bits
+ *     whenever the scale is a float32 value (53 >= 2 * 24 + 2 bits: the second rounding is innocuous), so
+ *     torch's CPU `/` agrees; a float32 multiply by the reciprocal -- torch's device-side `/ scale` -- does
+ *     not: it differs for 249 of the 65,536 readings at scale 6553.5, 38,850 at 1000, 19,860 at 5000.
+ *     use_max_depth != 0 and d >= max_depth: -1.0f is written (the reference's
+ *     `depth[depth >= 9.5] = -1`, the threshold a parameter).  A zero reading stays 0.0f: invalid to every
+ *     consumer (`gt > 0`), like -1.
+ *   small outputs: output k is present when both of its pointers are non-NULL and holds EXACTLY THE BITS
+ *     gsr_resize_frame produces from the full-size im / depth above: depth nearest, colour bilinear with the
+ *     integer-derived taps and the lerp that skips a zero weight.  They are formed from the raw bytes, every tap
+ *     converted on the fly -- im / depth are being written by the same launch and are never read -- and the bits
+ *     are the same because the conversion is a pure function of the byte.
+ * im / depth (both NULL) may be absent when only small frames are wanted; both small outputs may be absent too.
+ * Returns GSR_ERR_INVALID_ARG and launches nothing for: every size and overflow condition gsr_resize_frame
+ * refuses; a NULL rgb_hwc or depth_u16; im / depth or a small output with exactly one pointer NULL; all three
+ * outputs absent; png_depth_scale not finite or <= 0; use_max_depth != 0 with a NaN max_depth.  Errors name
+ * "ingest_frame". */
+int gsr_ingest_frame(int H, int W, const unsigned char* rgb_hwc, const unsigned short* depth_u16,
+                     double png_depth_scale, int use_max_depth, float max_depth, float* im, float* depth, int h0,
+                     int w0, float* im_out0, float* depth_out0, int h1, int w1, float* im_out1, float* depth_out1,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -233,6 +233,10 @@ SIGNATURES = {
     # include/gsr_glue.h: frame resize (H, W, im, depth, then {h, w, im_out, depth_out} twice, stream)
     "gsr_resize_frame": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p]),
+    # include/gsr_glue.h: raw frame ingest (H, W, rgb_hwc, depth_u16, png_depth_scale, use_max_depth, max_depth,
+    # im, depth, then {h, w, im_out, depth_out} twice, stream)
+    "gsr_ingest_frame": (c_int, [c_int, c_int, c_void_p, c_void_p, c_double, c_int, c_float, c_void_p, c_void_p,
+                                 c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -24,7 +24,7 @@ DIAG = os.path.join(HERE, "_diag")  # experiment / diagnostics libraries that tr
 FORWARD_STAGES = ["gsr_preprocess.hip", "gsr_binning.hip", "gsr_radix.hip", "gsr_forward.hip", "gsr_reuse.hip"]
 SOURCES = ["gsr_forward_unit.hip", "gsr_backward.hip", "gsr_backward_power.hip", "gsr_capi.hip", "gsr_timing.hip",
            "gsr_glue.hip", "gsr_mapping.hip", "gsr_sh.hip", "gsr_keyframe.hip", "gsr_eval.hip", "gsr_densify.hip",
-           "gsr_viewgain.hip", "gsr_resize.hip"]
+           "gsr_viewgain.hip", "gsr_resize.hip", "gsr_ingest.hip"]
 ARCH = os.environ.get("GSR_OFFLOAD_ARCH", "gfx950")
 
 

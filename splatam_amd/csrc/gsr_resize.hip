@@ -15,10 +15,12 @@
 // The source columns / rows and the weights come from integers (quotient and remainder of
 // ((2 x + 1) W - w) / (2 w)), never from a float scale, and every float operation is rounded on its
 // own (no contraction) in the order include/gsr_glue.h states, so resize.resize_literal's
-// elementwise torch ops form the same bits.
+// elementwise torch ops form the same bits.  The taps and the lerp are gsr_resize_taps.h's, which
+// gsr_ingest.hip shares.
 #include "../../include/gsr.h"
 #include "../../include/gsr_glue.h"
 #include "gsr_errors.h"
+#include "gsr_resize_taps.h"
 
 namespace gsr {
 namespace {
@@ -30,33 +32,6 @@ struct RsOut {
     float* im;
     float* depth;
 };
-
-// The left tap and the weight of the right one along an axis of n_in source and n_out output samples:
-// s = max(0, (i + 0.5) n_in / n_out - 0.5) = max(0, ((2 i + 1) n_in - n_out) / (2 n_out)).
-struct RsTap {
-    int i0, i1;
-    float t;
-};
-__device__ __forceinline__ RsTap rs_tap(int i, int n_in, int n_out) {
-    const int den = 2 * n_out;
-    const int num = (2 * i + 1) * n_in - n_out;  // (< 2 n_in n_out: the entry refuses sizes beyond an int)
-    RsTap r;
-    if (num <= 0) {
-        r.i0 = 0;
-        r.t = 0.f;
-    } else {
-        r.i0 = num / den;
-        r.t = (float)(num - r.i0 * den) / (float)den;
-    }
-    r.i1 = min(r.i0 + 1, n_in - 1);
-    return r;
-}
-
-// a + t (b - a); a tap of weight zero is not read into the result (a NaN or an infinity there stays out)
-__device__ __forceinline__ float rs_lerp(float a, float b, float t) {
-#pragma clang fp contract(off)
-    return t == 0.f ? a : a + t * (b - a);
-}
 
 __global__ void __launch_bounds__(RS_BLOCK)
 rs_resize_kernel(int H, int W, const float* __restrict__ im, const float* __restrict__ depth, RsOut o0, RsOut o1,

@@ -65,6 +65,15 @@ a frame with `w2c` (its pose relative to frame 0, tracking.use_gt_poses, :812-82
 add_new_gaussians' threshold there (:444-453; densify.depth_threshold, gsr_densify_frame_capped) and
 SlamSequence(params=None) builds the map from the first frame on the device (init_map_device: gsr_init_frame).
 
+That loop's frames arrive as the sensor delivers them (scripts/ros_handler.py:402-411): an interleaved uint8 image,
+a uint16 depth image and an odometry pose.  SlamSequence.push_raw(rgb_u8, depth_u16, pose=None, w2c=None) takes
+exactly that (png_depth_scale, max_depth): one gsr_ingest_frame launch (splatam_amd.ingest) writes the float
+frame and, under track_size / densify_size, the small frames -- no gsr_resize_frame launch for such a frame --
+and ingest.odometry_w2c makes the pose relative to the first one on the host.  Raw frames given at construction
+({"rgb_u8", "depth_u16"[, "pose"]}) are ingested before anything reads them.  arrival_report=True keeps the
+reference's on-arrival PSNR record (:431-446, 473-481) in `arrival`: every frame after the first rendered at its
+pose before its densification and mapping, one row of evaluate.COLUMNS each, nothing read back.
+
 The active-mapping node around that loop scores candidate views after every frame (scripts/ros_handler.py:251-359,
 807-836): SlamSequence.view_scorer builds fisher.SequenceFisher graphs on the padded map once, fit_visited and
 view_gains replay them on the map as it stands -- nothing on the frame() / push() path changes, and the scorer's
@@ -82,6 +91,7 @@ from .densify import make_workspace as make_densify_workspace
 from .keyframes import KeyframeBank, WordFeed, draw_words, make_workspace, pose_w2c, select_device, \
     select_literal, words_tensor
 from .mapper import GAUSS_KEYS, GraphMapper
+from .ingest import ingest_device, odometry_w2c
 from .resize import check_track_args, resize_device, resized_camera, scale_intrinsics
 from .slam import MappingConfig, TrackingConfig, build_rotation, color_key, matrix_to_quaternion, \
     transform_to_frame, transformed_params2depthplussilhouette
@@ -335,7 +345,7 @@ class _SequenceBase:
                "window", "keyframe_every", "sil_thres", "track_cfg", "map_cfg", "prune", "scene_radius",
                "keyframe_policy", "overlap_pixels", "densify_mode", "densify_frames", "densify_cam",
                "densify_intrinsics", "median_thr", "median_scale", "num_frames", "map_every", "track_frames",
-               "track_cam", "track_size", "densify_size")
+               "track_cam", "track_size", "densify_size", "png_depth_scale", "max_depth", "arrival_report")
 
     def _set_options(self, args: dict):
         """Stores the constructor arguments both classes take (OPTIONS, out of the constructor's locals()) as
@@ -347,20 +357,62 @@ class _SequenceBase:
             raise ValueError(f"num_frames {self.num_frames}: between 1 and num_frames frames to start with")
         if int(self.map_every) < 1:
             raise ValueError("map_every >= 1")
+        premade = self._ingest_given()
         check_densify_args(self.densify_mode, self.densify_frames, self.densify_cam, self.densify_intrinsics,
                            self.frames)
         check_track_args(self.track_frames, self.track_cam, self.frames)
-        self._set_sizes()
+        self._set_sizes(premade)
         self.overlap_pixels = int(self.overlap_pixels)
         if self.scene_radius is None:  # initialize_first_timestep: max depth / scene_radius_depth_ratio (3, the config's)
             self.scene_radius = self.frames[0]["depth"].max() / 3.0
         self.keyframes = [self._kf(0)]
         self.tracking_iters_run = []  # per frame() call: the tracking iterations run (0: frame 0, not tracked)
 
-    def _set_sizes(self):
+    def _owns_small_frames(self) -> bool:
+        """Whether the caller gives the small frames (track_frames / densify_frames without track_size /
+        densify_size): such a capture is not fed raw frames."""
+        return (self.track_frames is not None and self.track_size is None) or \
+            (self.densify_frames is not None and self.densify_size is None)
+
+    def _ingest_raw(self, rgb_u8: torch.Tensor, depth_u16: torch.Tensor) -> tuple:
+        """(frame, tracking frame, densification frame) of a raw sensor frame (splatam_amd.ingest: uint8 [H,W,3],
+        uint16 [H,W]) under png_depth_scale / max_depth and track_size / densify_size (None where the size is not
+        set): one gsr_ingest_frame launch for all of them, nothing read back."""
+        if self.png_depth_scale is None:
+            raise ValueError("a raw frame needs png_depth_scale (the sensor units per metre)")
+        ts, ds = self.track_size, self.densify_size
+        sizes = [s for s in (ts, ds) if s is not None]
+        out = ingest_device(rgb_u8, depth_u16, self.png_depth_scale, self.max_depth, *sizes)
+        if not sizes:
+            return out, None, None
+        smalls = list(out[1:])
+        return out[0], (smalls.pop(0) if ts is not None else None), (smalls.pop(0) if ds is not None else None)
+
+    def _ingest_given(self):
+        """Raw frames given at construction ({"rgb_u8", "depth_u16"[, "pose"]} each, with png_depth_scale): the
+        frame list becomes their float frames (a new list), before anything reads a frame.  Returns per frame
+        the (tracking frame, densification frame) the same launch made, for _set_sizes; None for float frames.
+        The first frame's "pose" (x, y, z, qx, qy, qz, qw), when given, is what push_raw's poses are relative to."""
+        self.initial_pose = None
+        raw = ["rgb_u8" in f for f in self.frames]
+        if not any(raw):
+            return None
+        if not all(raw):
+            raise ValueError("frames: raw ({'rgb_u8', 'depth_u16'}) or float ({'im', 'depth'}), not both")
+        if self._owns_small_frames():
+            raise ValueError("raw frames: a capture with track_frames / densify_frames owns its small frames")
+        given = self.frames
+        made = [self._ingest_raw(f["rgb_u8"], f["depth_u16"]) for f in given]
+        self.frames = [m[0] for m in made]
+        if given[0].get("pose") is not None:
+            self.initial_pose = np.array(given[0]["pose"], dtype=np.float64)
+        return [m[1:] for m in made]
+
+    def _set_sizes(self, premade=None):
         """track_size / densify_size (h, w): the sequence makes the small frames itself -- the camera (and the
         densification intrinsics) through splatam_amd.resize, the frames given so far by one gsr_resize_frame
-        launch each (_make_small).  Exclusive with track_frames / densify_frames."""
+        launch each (_make_small; `premade`: _ingest_given's, for raw frames, whose ingest launch made them).
+        Exclusive with track_frames / densify_frames."""
         if self.track_size is not None and self.track_frames is not None:
             raise ValueError("track_size: exclusive with track_frames / track_cam")
         if self.densify_size is not None and self.densify_frames is not None:
@@ -379,8 +431,8 @@ class _SequenceBase:
             self.densify_cam = resized_camera(W, H, self.intrinsics, *self.densify_size, dev, w2c=w2c)
             self.densify_intrinsics = scale_intrinsics(self.intrinsics, H, W, *self.densify_size)
             self.densify_frames = []
-        for f in self.frames:
-            tf, df = self._make_small(f)
+        for i, f in enumerate(self.frames):
+            tf, df = self._make_small(f) if premade is None else premade[i]
             if tf is not None:
                 self.track_frames.append(tf)
             if df is not None:
@@ -409,11 +461,12 @@ class _SequenceBase:
         """Whether frame t densifies and maps (map_every, scripts/splatam_realtime.py:844): frame 0 always."""
         return t == 0 or (t + 1) % int(self.map_every) == 0
 
-    def _append_frame(self, im: torch.Tensor, depth: torch.Tensor, densify_frame=None, track_frame=None) -> int:
+    def _append_frame(self, im: torch.Tensor, depth: torch.Tensor, densify_frame=None, track_frame=None,
+                      made=None) -> int:
         """A frame that arrived: appended to the frame list (and its densification frame to densify_frames, its
         tracking frame to track_frames, when the capture has those; under densify_size / track_size the sequence
-        makes them here, _make_small, and takes none).  Returns its index; ValueError beyond num_frames (the
-        pose columns)."""
+        makes them here, _make_small, and takes none -- unless `made`, the (tracking frame, densification frame)
+        _ingest_raw's launch made already).  Returns its index; ValueError beyond num_frames (the pose columns)."""
         t = len(self.frames)
         if self.num_frames is None or t >= int(self.num_frames):
             raise ValueError(f"frame {t}: the sequence holds num_frames = {self.num_frames} frames")
@@ -424,7 +477,7 @@ class _SequenceBase:
             raise ValueError("densify_frame: one per frame when the capture has densify_frames, else none")
         if self.track_size is None and (track_frame is None) != (self.track_frames is None):
             raise ValueError("track_frame: one per frame when the capture has track_frames, else none")
-        made_t, made_d = self._make_small({"im": im, "depth": depth})
+        made_t, made_d = self._make_small({"im": im, "depth": depth}) if made is None else made
         track_frame = made_t if track_frame is None else track_frame
         densify_frame = made_d if densify_frame is None else densify_frame
         self.frames.append({"im": im, "depth": depth})
@@ -433,6 +486,28 @@ class _SequenceBase:
         if track_frame is not None:
             self.track_frames.append(track_frame)
         return t
+
+    def _push_raw_frame(self, rgb_u8: torch.Tensor, depth_u16: torch.Tensor, pose=None, w2c=None) -> tuple:
+        """push_raw's intake: the checks, the one gsr_ingest_frame launch (_ingest_raw: the full frame and the
+        small ones, so _make_small is not called for this frame), the _append_frame bookkeeping and the pose.
+        Returns (t, w2c): `pose` (x, y, z, qx, qy, qz, qw) through ingest.odometry_w2c against the first pose
+        pushed (or the first raw frame's "pose"), on its way to the device by a non-blocking copy."""
+        if self.png_depth_scale is None:
+            raise ValueError("push_raw needs png_depth_scale (the sensor units per metre)")
+        if pose is not None and w2c is not None:
+            raise ValueError("push_raw: pose or w2c, not both")
+        if self._owns_small_frames():
+            raise ValueError("push_raw: a capture with track_frames / densify_frames owns its small frames "
+                             "(push_frames)")
+        if self.num_frames is None or len(self.frames) >= int(self.num_frames):
+            raise ValueError(f"frame {len(self.frames)}: the sequence holds num_frames = {self.num_frames} frames")
+        frame, tf, df = self._ingest_raw(rgb_u8, depth_u16)
+        t = self._append_frame(frame["im"], frame["depth"], made=(tf, df))
+        if pose is not None:
+            if self.initial_pose is None:
+                self.initial_pose = np.array(pose, dtype=np.float64)
+            w2c = odometry_w2c(self.initial_pose, pose, device=frame["depth"].device)
+        return t, w2c
 
     def _kf(self, t: int) -> dict:
         return {"cam": self.cam, "w2c": self.w2c, "im": self.frames[t]["im"], "depth": self.frames[t]["depth"], "id": t}
@@ -487,12 +562,14 @@ class SlamSequence(_SequenceBase):
                  scene_radius=None, keyframe_policy: str = "window", overlap_pixels: int = 1600,
                  densify_mode: str = "torch", densify_frames=None, densify_cam=None, densify_intrinsics=None,
                  median_thr=None, median_scale: float = 50.0, num_frames: int | None = None, map_every: int = 1,
-                 track_frames=None, track_cam=None, track_size=None, densify_size=None):
+                 track_frames=None, track_cam=None, track_size=None, densify_size=None, png_depth_scale=None,
+                 max_depth=None, arrival_report: bool = False):
         if params is not None and (color_key(params) != "rgb_colors" or params["log_scales"].shape[1] != 1):
             raise ValueError("SlamSequence: SplaTAM's isotropic rgb map (the tracking fast path's form)")
         if tracking_iters % track_replay:
             raise ValueError("tracking_iters must be a multiple of track_replay")
         self._set_options(locals())
+        frames = self.frames  # (raw frames given: their float frames, _ingest_given)
         self.bin_capacity, self.seed = int(bin_capacity), seed
         self.rng = np.random.RandomState(seed)
         self.draws = []  # per frame: the mapper's keyframe draws (window indices; None: the frame did not map); "overlap": the random words
@@ -508,6 +585,12 @@ class SlamSequence(_SequenceBase):
         if densify_mode == "device":
             d0 = (self.densify_frames if self.densify_frames is not None else frames)[0]["depth"]
             self.densify_workspace = make_densify_workspace(d0.shape[-2], d0.shape[-1], dev)
+        if arrival_report:
+            from . import evaluate as ev
+            d0 = frames[0]["depth"]
+            self.arrival = torch.full((self._n_frames(), 8), float("nan"), dtype=torch.float32, device=dev)
+            self.arrival_workspace = ev.make_workspace(d0.shape[-2], d0.shape[-1], dev, ms_ssim=False)
+            self.arrival_status = torch.zeros(4, dtype=torch.int32, device=dev)
         padded = None
         if params is None:  # the map is born from frame 0 (initialize_first_timestep), on the device
             kf, intr = self._densify_kf(0)
@@ -650,6 +733,8 @@ class SlamSequence(_SequenceBase):
                 ran = self.track(t)
             else:
                 write_given_pose(self.params, t, w2c)
+            if self.arrival_report:
+                self.report_arrival(t)
             if self._maps(t):
                 self.densify(t)
         self.tracking_iters_run.append(ran)
@@ -658,6 +743,20 @@ class SlamSequence(_SequenceBase):
         else:
             self.draws.append(None)
             self._add_keyframe(t)
+
+    def report_arrival(self, t: int):
+        """The reference's on-arrival record (scripts/ros_handler.py:431-446, 473-481: gain_psnr_arr's "psnr"):
+        frame t rendered at its pose column from the map as it stands BEFORE the frame's densification and
+        mapping (one evaluate.render_frame: the static forward under the alive mask), and the metrics of render
+        against frame under the valid-depth mask (one evaluate.frame_metrics, no MS-SSIM) into row t of
+        `arrival` [num_frames, 8] (evaluate.COLUMNS; NaN where nothing was reported: frame 0, the MS-SSIM
+        column).  Nothing is read back.  The gains of the same record are view_gains'."""
+        from . import evaluate as ev
+        f = self.frames[t]
+        im, ds = ev.render_frame(self.params, t, self.cam, self.w2c, self.alive, self.bin_capacity,
+                                 self.arrival_status)
+        ev.frame_metrics(im, ds, f["im"], f["depth"], self.sil_thres, self.arrival[t], self.arrival_workspace,
+                         use_sil_mask=False, ms_ssim=False)
 
     def run(self, frames=None):
         """frame(t) for every t of `frames` (an iterable; default: the frames in the list that have not run)."""
@@ -681,13 +780,26 @@ class SlamSequence(_SequenceBase):
         self.frame(t, w2c=w2c)
         return t
 
+    def push_raw(self, rgb_u8: torch.Tensor, depth_u16: torch.Tensor, pose=None, w2c=None) -> int:
+        """push() for the frame as the sensor delivers it (scripts/ros_handler.py:402-411): rgb_u8 [H,W,3] uint8,
+        depth_u16 [H,W] uint16 in sensor units (png_depth_scale per metre; max_depth marks far readings -1) --
+        splatam_amd.ingest.  One gsr_ingest_frame launch makes the float frame and, under track_size /
+        densify_size, the small frames (no gsr_resize_frame launch for this frame); then push_frames'
+        bookkeeping and frame(t, w2c=...).  pose: the odometry pose (x, y, z, qx, qy, qz, qw), made relative to
+        the first pose pushed (ingest.odometry_w2c; host float64, a non-blocking copy to the device); w2c: as
+        in push().  ValueError: both given, no png_depth_scale, or a capture with explicit track_frames /
+        densify_frames (those callers own their small frames: push_frames).  Returns t.  Nothing is read back."""
+        t, w2c = self._push_raw_frame(rgb_u8, depth_u16, pose, w2c)
+        self.frame(t, w2c=w2c)
+        return t
+
     def check(self):
         """One host synchronisation: raises if a binning capacity or the map capacity overflowed."""
         if self.tracker.overflowed() or self.mapper.overflowed() or bool(self.overflow.item()):
             raise RuntimeError("SlamSequence: a binning capacity or the map capacity was exceeded")
-        st = self.dstatus.cpu()
-        if int(st[0]) > self.bin_capacity or int(st[1]) != 0:
-            raise RuntimeError("SlamSequence: the densification render overflowed its binning capacity")
+        st = [self.dstatus.cpu()] + ([self.arrival_status.cpu()] if self.arrival_report else [])
+        if any(int(s[0]) > self.bin_capacity or int(s[1]) != 0 for s in st):
+            raise RuntimeError("SlamSequence: the densification (or arrival) render overflowed its binning capacity")
 
     def evaluate(self, gt_w2c=None, eval_every: int = 1, ms_ssim: bool = True) -> dict:
         """The reference's end-of-run eval() (utils/eval_helpers.py:408-640) of the padded map as it stands
@@ -842,8 +954,10 @@ class PerFrameSlam(_SequenceBase):
                  bin_capacity: int | None = None, keyframe_policy: str = "window", overlap_pixels: int = 1600,
                  densify_mode: str = "torch", densify_frames=None, densify_cam=None, densify_intrinsics=None,
                  median_thr=None, median_scale: float = 50.0, num_frames: int | None = None, map_every: int = 1,
-                 track_frames=None, track_cam=None, track_size=None, densify_size=None):
+                 track_frames=None, track_cam=None, track_size=None, densify_size=None, png_depth_scale=None,
+                 max_depth=None, arrival_report: bool = False):
         self._set_options(locals())
+        self.arrival = {}  # arrival_report: per reported frame, evaluate_literal's row of the on-arrival render
         self.kf_list = []  # "overlap": the keyframes in the order appended, each with its est_w2c snapshot
         self.windows = []  # "overlap": per frame, the selected window's time indices
         self.p = {k: v.detach().clone() for k, v in params.items()}
@@ -865,6 +979,11 @@ class PerFrameSlam(_SequenceBase):
             with torch.no_grad():
                 p["cam_unnorm_rots"][..., t] = tp["cam_unnorm_rots"][..., 0]
                 p["cam_trans"][..., t] = tp["cam_trans"][..., 0]
+        if t > 0 and self.arrival_report:  # (SlamSequence.report_arrival's point, in plain renders and torch ops)
+            from . import evaluate as ev
+            f = self.frames[t]
+            self.arrival[t] = ev.evaluate_literal(*ev.render_frame(p, t, self.cam, self.w2c), f["im"], f["depth"],
+                                                  self.sil_thres, ms_ssim=False)
         if t > 0 and self._maps(t):
             kf, intr = self._densify_kf(t)
             add = add_new_gaussians_device if self.densify_mode == "device" else add_new_gaussians_literal
@@ -885,6 +1004,13 @@ class PerFrameSlam(_SequenceBase):
             mp, _, _ = m.compact()
         self.p = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in mp.items()}
         self._add_keyframe(t)
+
+    def push_raw(self, rgb_u8: torch.Tensor, depth_u16: torch.Tensor, sequence=None, pose=None, w2c=None) -> int:
+        """SlamSequence.push_raw for this loop: the same intake (one gsr_ingest_frame launch, the bookkeeping,
+        the pose), then frame(t, sequence, w2c=...) with the mapper's draws `sequence`.  Needs num_frames."""
+        t, w2c = self._push_raw_frame(rgb_u8, depth_u16, pose, w2c)
+        self.frame(t, sequence, w2c=w2c)
+        return t
 
     def _add_keyframe(self, t: int):
         if not self._is_keyframe(t):
