@@ -50,6 +50,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from . import dist as sd
+from ._devcall import check_rc
 from .rasterizer import GaussianRasterizer
 
 SEED = 1e-3      # im.backward(gradient=torch.ones_like(im) * 1e-3)  (ros_handler.py:888)
@@ -69,10 +70,8 @@ def camera_points(means: torch.Tensor, w2c: torch.Tensor) -> torch.Tensor:
     means = means.detach().float().contiguous()
     w2c = w2c.detach().to(means.device).float().contiguous()
     pts = torch.empty_like(means)
-    rc = lib.gsr_points_to_camera(means.shape[0], means.data_ptr(), w2c.data_ptr(), pts.data_ptr(),
-                                  torch.cuda.current_stream(means.device).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"gsr_points_to_camera: {lib.gsr_last_error().decode(errors='replace')}")
+    check_rc(lib.gsr_points_to_camera(means.shape[0], means.data_ptr(), w2c.data_ptr(), pts.data_ptr(),
+                                      torch.cuda.current_stream(means.device).cuda_stream), "gsr_points_to_camera")
     return pts
 
 
@@ -90,8 +89,7 @@ def _count_into(cam, P: int, n: int, geom, binning, img, sil_thres: float, out: 
     rc = lib.gsr_silhouette_count(ctypes.byref(st), int(P), int(n), ptr(geom), ptr(binning), ptr(img),
                                   float(sil_thres), out.data_ptr(), stream)
     del keep
-    if rc != 0:
-        raise RuntimeError(f"gsr_silhouette_count: {lib.gsr_last_error().decode(errors='replace')}")
+    check_rc(rc, "gsr_silhouette_count")
 
 
 def silhouette_count(scorer: "FisherScorer", w2c: torch.Tensor, sil_thres: float = 0.5) -> torch.Tensor:
@@ -274,7 +272,152 @@ class FisherScorer:
         return out
 
 
-class BatchedFisher:
+class _PoseBatchGraph:
+    """What BatchedFisher and SequenceFisher share: K pose slots rendered per HIP-graph launch.  The slots (`w2c`
+    [K,4,4], `weight` [K], `H_inv` [P,4], `status` [K,4], `counts` [K] in mode "gains", the backward's `seed`),
+    the warm-up and the capture, and the calls that load the slots, replay and read the status.  A subclass sets
+    `cam`, `alive` (the forward's mask, or None) and `capacity` (the forward's binning capacity) and gives
+    _rendervars, _scores_out, _score and _scores_result."""
+
+    @staticmethod
+    def _check_mode(mode: str, log_scales: torch.Tensor):
+        if mode not in ("sum", "scores", "gains"):
+            raise ValueError("mode is 'sum', 'scores' or 'gains'")
+        if mode == "gains" and log_scales.shape[-1] != 1:
+            raise ValueError("mode 'gains' takes an isotropic map only (log_scales [P,1]): the reference's "
+                             "silhouette render rotates the Gaussians, its Hessian render does not")
+
+    def _make_slots(self, cam, P: int, dev, K: int, mode: str, sil_thres: float):
+        self.cam, self.K, self.mode, self.sil_thres = cam, int(K), mode, float(sil_thres)
+        self.w2c = torch.eye(4, device=dev).repeat(self.K, 1, 1).contiguous()
+        self.weight = torch.zeros(self.K, device=dev)
+        self.H_inv = torch.zeros(P, 4, device=dev)
+        self.status = torch.zeros(self.K, 4, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(self.K, dtype=torch.int32, device=dev) if mode == "gains" else None
+        self.seed = torch.full((3, cam.image_height, cam.image_width), SEED, device=dev)  # ros_handler.py:888
+        self.e = torch.Tensor([])
+
+    def _capture(self):
+        from . import _C
+        dev = self.H_inv.device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._body(_C)  # warm-up (allocator pools, kernels) outside the capture
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.status.zero_()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=side):
+            self._body(_C)
+
+    def _forward(self, _C, pts, rv, capacity, k):
+        """The forward of camera-frame points `pts`; static (capacity > 0) into status row k."""
+        cam = self.cam
+        _, colors, opac, scales, rot = rv
+        return _C.rasterize_gaussians(cam.bg, pts, colors, opac, scales, rot, cam.scale_modifier, self.e,
+                                      cam.viewmatrix, cam.projmatrix, cam.tanfovx, cam.tanfovy, cam.image_height,
+                                      cam.image_width, self.e, cam.sh_degree, cam.campos, cam.prefiltered,
+                                      capacity=capacity, status=self.status[k] if capacity else None,
+                                      alive=self.alive)
+
+    def _grads(self, _C, k, rv):
+        """(dL/dmeans_cam [P,3], dL/dopacity [P,1]) of pose slot k (power-2 backward, Fisher kernels)."""
+        cam = self.cam
+        _, colors, _, scales, rot = rv
+        pts = camera_points(rv[0], self.w2c[k])
+        n, _, radii, geom, binning, img, _ = self._forward(_C, pts, rv, self.capacity, k)
+        if self.mode == "gains":  # the silhouette count on this forward's lists, ahead of the backward
+            _count_into(cam, pts.shape[0], n, geom, binning, img, self.sil_thres, self.counts[k:k + 1])
+        g = _C.rasterize_gaussians_backward(cam.bg, pts, radii, colors, scales, rot, cam.scale_modifier, self.e,
+                                            cam.viewmatrix, cam.projmatrix, cam.tanfovx, cam.tanfovy, self.seed,
+                                            self.e, cam.sh_degree, cam.campos, geom, n, binning, img, 2,
+                                            needs=FISHER_NEEDS)
+        return g[3], g[2]
+
+    def _body(self, _C):
+        from ._lib import lib
+        with torch.no_grad():
+            rv = self._rendervars()
+            if self.mode == "sum":
+                self.out = torch.zeros_like(self.H_inv)
+                P = self.out.shape[0]
+                stream = torch.cuda.current_stream(self.out.device).cuda_stream
+                for k in range(self.K):
+                    dm, dop = self._grads(_C, k, rv)
+                    # out += [dm, dop] * weight[k] in one launch (bitwise torch's add_(cat(...) * w))
+                    check_rc(lib.gsr_fisher_accumulate(P, dm.data_ptr(), dop.data_ptr(),
+                                                       self.weight.data_ptr() + 4 * k, self.out.data_ptr(), stream),
+                             "gsr_fisher_accumulate")
+            else:
+                self.out = self._scores_out()
+                for k in range(self.K):
+                    self._score(k, *self._grads(_C, k, rv))
+
+    def _load(self, w2cs):
+        if len(w2cs) > self.K:
+            raise ValueError(f"at most {self.K} poses per launch")
+        with torch.no_grad():
+            self.weight.zero_()
+            for k, w in enumerate(w2cs):
+                self.w2c[k].copy_(w)
+                self.weight[k] = 1.0
+
+    def _replay(self, n: int, check: bool) -> bool:
+        """One graph launch on the loaded slots; with `check` (one host sync) False when one of the first n
+        slots exceeded the binning capacity."""
+        if check:
+            self.status.zero_()
+        self.graph.replay()
+        return not (check and self.overflowed(n))
+
+    def hessian_sum(self, w2cs, check: bool = True) -> torch.Tensor | None:
+        """sum over the (<= K) poses of H(w2c) [P,4] (one graph launch; on a padded map over the padded rows,
+        the dead ones +0).  With `check` (one host sync) returns None when a pose of this launch exceeded the
+        binning capacity (its Hessian would be missing from the sum): the caller re-renders the chunk eagerly
+        or rebuilds with more headroom."""
+        if self.mode != "sum":
+            raise RuntimeError(f"built for mode='{self.mode}'")
+        self._load(w2cs)
+        return self.out if self._replay(len(w2cs), check) else None
+
+    def scores(self, w2cs, H_inv, check: bool = True) -> torch.Tensor | None:
+        """sum(H(w2c_k) * H_inv) for each of the (<= K) poses against H_inv [P,4] (on a padded map the padded
+        rows; the dead ones are not read): float64 [n] (one graph launch); None on a capacity overflow of any
+        of them (see hessian_sum)."""
+        if self.mode != "scores":
+            raise RuntimeError(f"built for mode='{self.mode}'")
+        return self._replay_scores(w2cs, H_inv, check)
+
+    def _replay_scores(self, w2cs, H_inv, check):
+        self._load(w2cs)
+        if H_inv is not self.H_inv:  # (a caller may fill self.H_inv in place and pass it)
+            with torch.no_grad():
+                self.H_inv.copy_(H_inv)
+        return self._scores_result(len(w2cs)) if self._replay(len(w2cs), check) else None
+
+    def gains(self, w2cs, H_inv, k_sil: float = 1.0, k_eig: float = 1.0, k_sum: float = 1.0, nl_sil: bool = False,
+              nl_eig: bool = False, check: bool = True) -> torch.Tensor | None:
+        """send_gains' (g_sil, g_eig, gain) for each of the (<= K) poses: float64 [n,3] on the device (one graph
+        launch, then combine_gains); None on a capacity overflow of any of them (see hessian_sum).  The raw
+        counts of the launch stay in `counts[:n]`."""
+        if self.mode != "gains":
+            raise RuntimeError(f"built for mode='{self.mode}'")
+        eig = self._replay_scores(w2cs, H_inv, check)
+        if eig is None:
+            return None
+        cam = self.cam
+        return combine_gains(self.counts[:len(w2cs)], eig, cam.image_width * cam.image_height, k_sil, k_eig, k_sum,
+                             nl_sil, nl_eig)
+
+    def overflowed(self, n: int | None = None) -> bool:
+        """True if a replay since the last status reset exceeded the capacity in one of the first `n`
+        slots (default: all K; padded slots render the previous poses and are not results)."""
+        st = self.status[: self.K if n is None else n].cpu()
+        return bool((st[:, 0] > self.capacity).any() or (st[:, 2] > st[:, 3]).any() or (st[:, 1] != 0).any())
+
+
+class BatchedFisher(_PoseBatchGraph):
     """K poses of FisherScorer's Hessian per HIP-graph launch.
 
     mode "sum": `hessian_sum(w2cs)` returns sum_k H(w2c_k) (compute_H_visited_inv's H_train before the
@@ -290,152 +433,41 @@ class BatchedFisher:
     comes from eager probes of `probe_w2cs` times `headroom`; `overflowed()` reports (sticky) whether a
     replay exceeded it (results then invalid: rebuild with more headroom)."""
 
+    alive = None  # (the compact map of a FisherScorer: every row is live)
+
     def __init__(self, scorer: FisherScorer, K: int, mode: str = "sum", probe_w2cs=None, headroom: float = 1.5,
                  min_extra: int = 65536, sil_thres: float = 0.5):
         if scorer._hessian_fn is not None:
             raise RuntimeError("BatchedFisher renders through the rasterizer (no hessian_fn override)")
-        if mode not in ("sum", "scores", "gains"):
-            raise ValueError("mode is 'sum', 'scores' or 'gains'")
-        if mode == "gains" and scorer.params["log_scales"].shape[-1] != 1:
-            raise ValueError("mode 'gains' takes an isotropic map only (log_scales [P,1]): the reference's "
-                             "silhouette render rotates the Gaussians, its Hessian render does not")
+        self._check_mode(mode, scorer.params["log_scales"])
         from . import _C
-        self.sc, self.K, self.mode = scorer, int(K), mode
-        self.sil_thres = float(sil_thres)
-        cam = scorer.cam
-        means = scorer.params["means3D"].detach().contiguous()
+        self.sc = scorer
+        self.means = means = scorer.params["means3D"].detach().contiguous()
         dev = means.device
-        self.means = means
-        P = means.shape[0]
-        self.w2c = torch.eye(4, device=dev).repeat(self.K, 1, 1).contiguous()
-        self.weight = torch.zeros(self.K, device=dev)
-        self.H_inv = torch.zeros(P, 4, device=dev)
-        self.status = torch.zeros(self.K, 4, dtype=torch.int32, device=dev)
-        self.counts = torch.zeros(self.K, dtype=torch.int32, device=dev) if mode == "gains" else None
-        self.seed = torch.full((3, cam.image_height, cam.image_width), SEED, device=dev)  # ros_handler.py:888
-        self.e = torch.Tensor([])
+        self._make_slots(scorer.cam, means.shape[0], dev, K, mode, sil_thres)
+        rv = self._rendervars()
         probes = list(probe_w2cs) if probe_w2cs is not None else [torch.eye(4, device=dev)]
         n = 0
         with torch.no_grad():
             for w in probes:
                 pts = camera_points(means, w.to(dev).float())
-                n = max(n, self._forward(_C, pts, 0)[0])
+                n = max(n, self._forward(_C, pts, rv, 0, 0)[0])
         self.capacity = max(1, int(headroom * n) + int(min_extra))
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self._body(_C)  # warm-up (allocator pools, kernels) outside the capture
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.status.zero_()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=side):
-            self._body(_C)
+        self._capture()
 
-    def _forward(self, _C, pts, capacity):
-        sc, cam = self.sc, self.sc.cam
-        return _C.rasterize_gaussians(cam.bg, pts, sc.colors.detach(), sc.opacities.detach(), sc.scales.detach(),
-                                      sc.rotations.detach(), cam.scale_modifier, self.e, cam.viewmatrix,
-                                      cam.projmatrix, cam.tanfovx, cam.tanfovy, cam.image_height, cam.image_width,
-                                      self.e, cam.sh_degree, cam.campos, cam.prefiltered, capacity=capacity,
-                                      status=self.status[self._k] if capacity else None)
+    def _rendervars(self):
+        """The scorer's precomputed rendervars (FisherScorer.__init__)."""
+        sc = self.sc
+        return self.means, sc.colors.detach(), sc.opacities.detach(), sc.scales.detach(), sc.rotations.detach()
 
-    def _grads(self, _C, k):
-        """(dL/dmeans_cam [P,3], dL/dopacity [P,1]) of pose slot k (power-2 backward, Fisher kernels)."""
-        sc, cam = self.sc, self.sc.cam
-        self._k = k
-        pts = camera_points(self.means, self.w2c[k])
-        n, color, radii, geom, binning, img, depth = self._forward(_C, pts, self.capacity)
-        if self.mode == "gains":  # the silhouette count on this forward's lists, ahead of the backward
-            _count_into(cam, pts.shape[0], n, geom, binning, img, self.sil_thres, self.counts[k:k + 1])
-        g = _C.rasterize_gaussians_backward(cam.bg, pts, radii, sc.colors.detach(), sc.scales.detach(),
-                                            sc.rotations.detach(), cam.scale_modifier, self.e, cam.viewmatrix,
-                                            cam.projmatrix, cam.tanfovx, cam.tanfovy, self.seed, self.e,
-                                            cam.sh_degree, cam.campos, geom, n, binning, img, 2,
-                                            needs=FISHER_NEEDS)
-        return g[3], g[2]
+    def _scores_out(self):
+        return torch.zeros(self.K, dtype=torch.float32, device=self.H_inv.device)
 
-    def _body(self, _C):
-        from ._lib import lib
-        self._k = 0
-        with torch.no_grad():
-            if self.mode == "sum":
-                self.out = torch.zeros_like(self.H_inv)
-                P = self.out.shape[0]
-                stream = torch.cuda.current_stream(self.out.device).cuda_stream
-                for k in range(self.K):
-                    dm, dop = self._grads(_C, k)
-                    # out += [dm, dop] * weight[k] in one launch (bitwise torch's add_(cat(...) * w))
-                    rc = lib.gsr_fisher_accumulate(P, dm.data_ptr(), dop.data_ptr(),
-                                                   self.weight.data_ptr() + 4 * k, self.out.data_ptr(), stream)
-                    if rc != 0:
-                        raise RuntimeError(f"gsr_fisher_accumulate: {lib.gsr_last_error().decode(errors='replace')}")
-            else:
-                self.out = torch.zeros(self.K, dtype=torch.float32, device=self.H_inv.device)
-                for k in range(self.K):
-                    dm, dop = self._grads(_C, k)
-                    self.out[k] = (torch.cat([dm, dop.reshape(-1, 1)], dim=1) * self.H_inv).sum()
+    def _score(self, k, dm, dop):  # compute_eig_score in float32 torch ops
+        self.out[k] = (torch.cat([dm, dop.reshape(-1, 1)], dim=1) * self.H_inv).sum()
 
-    def _load(self, w2cs):
-        if len(w2cs) > self.K:
-            raise ValueError(f"at most {self.K} poses per launch")
-        with torch.no_grad():
-            self.weight.zero_()
-            for k, w in enumerate(w2cs):
-                self.w2c[k].copy_(w)
-                self.weight[k] = 1.0
-
-    def hessian_sum(self, w2cs, check: bool = True) -> torch.Tensor | None:
-        """sum over the (<= K) poses of H(w2c) [P,4] (one graph launch).  With `check` (one host sync)
-        returns None when a pose of this launch exceeded the binning capacity (its Hessian would be
-        missing from the sum): the caller re-renders the chunk eagerly or rebuilds with more headroom."""
-        if self.mode != "sum":
-            raise RuntimeError(f"built for mode='{self.mode}'")
-        self._load(w2cs)
-        if check:
-            self.status.zero_()
-        self.graph.replay()
-        if check and self.overflowed(len(w2cs)):
-            return None
-        return self.out
-
-    def scores(self, w2cs, H_inv, check: bool = True) -> torch.Tensor | None:
-        """sum(H(w2c_k) * H_inv) for each of the (<= K) poses, float64 (one graph launch); None on a
-        capacity overflow of any of them (see hessian_sum)."""
-        if self.mode != "scores":
-            raise RuntimeError(f"built for mode='{self.mode}'")
-        return self._replay_scores(w2cs, H_inv, check)
-
-    def _replay_scores(self, w2cs, H_inv, check):
-        self._load(w2cs)
-        with torch.no_grad():
-            self.H_inv.copy_(H_inv)
-        if check:
-            self.status.zero_()
-        self.graph.replay()
-        if check and self.overflowed(len(w2cs)):
-            return None
-        return self.out[:len(w2cs)].double()
-
-    def gains(self, w2cs, H_inv, k_sil: float = 1.0, k_eig: float = 1.0, k_sum: float = 1.0, nl_sil: bool = False,
-              nl_eig: bool = False, check: bool = True) -> torch.Tensor | None:
-        """send_gains' (g_sil, g_eig, gain) for each of the (<= K) poses: float64 [n,3] on the device (one graph
-        launch, then combine_gains); None on a capacity overflow of any of them (see hessian_sum).  The raw
-        counts of the launch stay in `counts[:n]`."""
-        if self.mode != "gains":
-            raise RuntimeError(f"built for mode='{self.mode}'")
-        eig = self._replay_scores(w2cs, H_inv, check)
-        if eig is None:
-            return None
-        cam = self.sc.cam
-        return combine_gains(self.counts[:len(w2cs)], eig, cam.image_width * cam.image_height, k_sil, k_eig, k_sum,
-                             nl_sil, nl_eig)
-
-    def overflowed(self, n: int | None = None) -> bool:
-        """True if a replay since the last status reset exceeded the capacity in one of the first `n`
-        slots (default: all K; padded slots render the previous poses and are not results)."""
-        st = self.status[: self.K if n is None else n].cpu()
-        return bool((st[:, 0] > self.capacity).any() or (st[:, 2] > st[:, 3]).any() or (st[:, 1] != 0).any())
+    def _scores_result(self, n):
+        return self.out[:n].double()
 
 
 def fisher_score(dmeans: torch.Tensor, dopac: torch.Tensor, H_inv: torch.Tensor, alive, workspace: torch.Tensor,
@@ -446,6 +478,7 @@ def fisher_score(dmeans: torch.Tensor, dopac: torch.Tensor, H_inv: torch.Tensor,
     from ._lib import lib
     P = dmeans.shape[0]
     dev = out.device
+    # (hand checks: _devcall.require words its message otherwise)
     for name, t, n in (("dmeans", dmeans, 3 * P), ("dopac", dopac, P), ("H_inv", H_inv, 4 * P)):
         if t.device != dev or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
             raise RuntimeError(f"fisher_score: {name} must be a contiguous float32 tensor of {n} values on {dev}")
@@ -457,10 +490,8 @@ def fisher_score(dmeans: torch.Tensor, dopac: torch.Tensor, H_inv: torch.Tensor,
     if workspace.device != dev or workspace.numel() * workspace.element_size() < lib.gsr_fisher_score_workspace_bytes():
         raise RuntimeError("fisher_score: workspace too small (score_workspace)")
     ptr = lambda t: t.data_ptr() if (t is not None and t.numel()) else None  # noqa: E731
-    rc = lib.gsr_fisher_score(int(P), ptr(dmeans), ptr(dopac), ptr(H_inv), ptr(alive), workspace.data_ptr(),
-                              out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"gsr_fisher_score: {lib.gsr_last_error().decode(errors='replace')}")
+    check_rc(lib.gsr_fisher_score(int(P), ptr(dmeans), ptr(dopac), ptr(H_inv), ptr(alive), workspace.data_ptr(),
+                                  out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "gsr_fisher_score")
 
 
 def score_workspace(device) -> torch.Tensor:
@@ -469,7 +500,7 @@ def score_workspace(device) -> torch.Tensor:
     return torch.zeros(int(lib.gsr_fisher_score_workspace_bytes()), dtype=torch.uint8, device=device)
 
 
-class SequenceFisher:
+class SequenceFisher(_PoseBatchGraph):
     """BatchedFisher on a running sequence's capacity-padded map (splatam_amd.sequence), captured once for the
     life of the buffers: K poses per HIP-graph launch, read from the map in place.
 
@@ -488,11 +519,7 @@ class SequenceFisher:
 
     def __init__(self, params: dict, alive: torch.Tensor, cam, K: int, mode: str = "sum", bin_capacity: int = 0,
                  sil_thres: float = 0.5):
-        if mode not in ("sum", "scores", "gains"):
-            raise ValueError("mode is 'sum', 'scores' or 'gains'")
-        if mode == "gains" and params["log_scales"].shape[-1] != 1:
-            raise ValueError("mode 'gains' takes an isotropic map only (log_scales [P,1]): the reference's "
-                             "silhouette render rotates the Gaussians, its Hessian render does not")
+        self._check_mode(mode, params["log_scales"])
         if int(K) < 1 or int(bin_capacity) <= 0:
             raise ValueError("SequenceFisher: K >= 1 and bin_capacity > 0 (the static forward's binning capacity)")
         means = params["means3D"]
@@ -501,29 +528,12 @@ class SequenceFisher:
             raise RuntimeError("Fisher scoring runs on ROCm devices only (no CPU fallback)")
         if alive.dtype != torch.uint8 or alive.numel() != P or alive.device != dev or not alive.is_contiguous():
             raise RuntimeError("alive: contiguous uint8 [P] on the parameters' device")
-        from . import _C
-        self.params, self.alive, self.cam = params, alive, cam
-        self.K, self.mode, self.capacity, self.sil_thres = int(K), mode, int(bin_capacity), float(sil_thres)
-        self.w2c = torch.eye(4, device=dev).repeat(self.K, 1, 1).contiguous()
-        self.weight = torch.zeros(self.K, device=dev)
-        self.H_inv = torch.zeros(P, 4, device=dev)
-        self.status = torch.zeros(self.K, 4, dtype=torch.int32, device=dev)
-        self.counts = torch.zeros(self.K, dtype=torch.int32, device=dev) if mode == "gains" else None
-        self.seed = torch.full((3, cam.image_height, cam.image_width), SEED, device=dev)  # ros_handler.py:888
-        self.e = torch.Tensor([])
+        self.params, self.alive, self.capacity = params, alive, int(bin_capacity)
+        self._make_slots(cam, P, dev, K, mode, sil_thres)
         if mode != "sum":
             self.out = torch.zeros(self.K, dtype=torch.float64, device=dev)
             self.workspace = score_workspace(dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self._body(_C)  # warm-up (allocator pools, kernels) outside the capture
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.status.zero_()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, stream=side):
-            self._body(_C)
+        self._capture()
 
     def _rendervars(self):
         """The map's rendervars as FisherScorer.__init__ forms them (ros_handler.py:868-874), once per replay."""
@@ -534,98 +544,11 @@ class SequenceFisher:
         scales = torch.tile(scales, (1, 3)) if scales.shape[-1] == 1 else scales
         return p["means3D"].detach(), p["rgb_colors"].detach(), opac, scales, rot
 
-    def _grads(self, _C, k, rv):
-        """(dL/dmeans_cam [P,3], dL/dopacity [P,1]) of pose slot k (power-2 backward, Fisher kernels)."""
-        cam = self.cam
-        means, colors, opac, scales, rot = rv
-        pts = camera_points(means, self.w2c[k])
-        n, _, radii, geom, binning, img, _ = _C.rasterize_gaussians(
-            cam.bg, pts, colors, opac, scales, rot, cam.scale_modifier, self.e, cam.viewmatrix, cam.projmatrix,
-            cam.tanfovx, cam.tanfovy, cam.image_height, cam.image_width, self.e, cam.sh_degree, cam.campos,
-            cam.prefiltered, capacity=self.capacity, status=self.status[k], alive=self.alive)
-        if self.mode == "gains":  # the silhouette count on this forward's lists, ahead of the backward
-            _count_into(cam, pts.shape[0], n, geom, binning, img, self.sil_thres, self.counts[k:k + 1])
-        g = _C.rasterize_gaussians_backward(cam.bg, pts, radii, colors, scales, rot, cam.scale_modifier, self.e,
-                                            cam.viewmatrix, cam.projmatrix, cam.tanfovx, cam.tanfovy, self.seed,
-                                            self.e, cam.sh_degree, cam.campos, geom, n, binning, img, 2,
-                                            needs=FISHER_NEEDS)
-        return g[3], g[2]
+    def _scores_out(self):
+        return self.out  # (preallocated: gsr_fisher_score writes its elements)
 
-    def _body(self, _C):
-        from ._lib import lib
-        with torch.no_grad():
-            rv = self._rendervars()
-            P = self.H_inv.shape[0]
-            if self.mode == "sum":
-                self.out = torch.zeros_like(self.H_inv)
-                stream = torch.cuda.current_stream(self.out.device).cuda_stream
-                for k in range(self.K):
-                    dm, dop = self._grads(_C, k, rv)
-                    rc = lib.gsr_fisher_accumulate(P, dm.data_ptr(), dop.data_ptr(),
-                                                   self.weight.data_ptr() + 4 * k, self.out.data_ptr(), stream)
-                    if rc != 0:
-                        raise RuntimeError(f"gsr_fisher_accumulate: {lib.gsr_last_error().decode(errors='replace')}")
-            else:
-                for k in range(self.K):
-                    dm, dop = self._grads(_C, k, rv)
-                    fisher_score(dm, dop, self.H_inv, self.alive, self.workspace, self.out[k:k + 1])
+    def _score(self, k, dm, dop):
+        fisher_score(dm, dop, self.H_inv, self.alive, self.workspace, self.out[k:k + 1])
 
-    def _load(self, w2cs):
-        if len(w2cs) > self.K:
-            raise ValueError(f"at most {self.K} poses per launch")
-        with torch.no_grad():
-            self.weight.zero_()
-            for k, w in enumerate(w2cs):
-                self.w2c[k].copy_(w)
-                self.weight[k] = 1.0
-
-    def hessian_sum(self, w2cs, check: bool = True) -> torch.Tensor | None:
-        """sum over the (<= K) poses of H(w2c) over the padded rows [P,4] (one graph launch; dead rows +0).
-        With `check` (one host sync) None when a pose of this launch exceeded the binning capacity."""
-        if self.mode != "sum":
-            raise RuntimeError(f"built for mode='{self.mode}'")
-        self._load(w2cs)
-        if check:
-            self.status.zero_()
-        self.graph.replay()
-        if check and self.overflowed(len(w2cs)):
-            return None
-        return self.out
-
-    def scores(self, w2cs, H_inv, check: bool = True) -> torch.Tensor | None:
-        """gsr_fisher_score of each of the (<= K) poses against H_inv [P,4] (padded rows; the dead ones are not
-        read): float64 [n] (one graph launch); None on a capacity overflow of any of them (`check`)."""
-        if self.mode != "scores":
-            raise RuntimeError(f"built for mode='{self.mode}'")
-        return self._replay_scores(w2cs, H_inv, check)
-
-    def _replay_scores(self, w2cs, H_inv, check):
-        self._load(w2cs)
-        if H_inv is not self.H_inv:  # (a caller may fill self.H_inv in place and pass it)
-            with torch.no_grad():
-                self.H_inv.copy_(H_inv)
-        if check:
-            self.status.zero_()
-        self.graph.replay()
-        if check and self.overflowed(len(w2cs)):
-            return None
-        return self.out[:len(w2cs)].clone()
-
-    def gains(self, w2cs, H_inv, k_sil: float = 1.0, k_eig: float = 1.0, k_sum: float = 1.0, nl_sil: bool = False,
-              nl_eig: bool = False, check: bool = True) -> torch.Tensor | None:
-        """send_gains' (g_sil, g_eig, gain) for each of the (<= K) poses: float64 [n,3] on the device (one graph
-        launch, then combine_gains); None on a capacity overflow (`check`).  The raw counts stay in `counts[:n]`."""
-        if self.mode != "gains":
-            raise RuntimeError(f"built for mode='{self.mode}'")
-        eig = self._replay_scores(w2cs, H_inv, check)
-        if eig is None:
-            return None
-        cam = self.cam
-        return combine_gains(self.counts[:len(w2cs)], eig, cam.image_width * cam.image_height, k_sil, k_eig, k_sum,
-                             nl_sil, nl_eig)
-
-    def overflowed(self, n: int | None = None) -> bool:
-        """True if a replay since the last status reset exceeded the capacity in one of the first `n`
-        slots (default: all K; padded slots render the previous poses and are not results)."""
-        st = self.status[: self.K if n is None else n].cpu()
-        return bool((st[:, 0] > self.capacity).any() or (st[:, 2] > st[:, 3]).any() or (st[:, 1] != 0).any())
+    def _scores_result(self, n):
+        return self.out[:n].clone()

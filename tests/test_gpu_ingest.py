@@ -9,6 +9,8 @@ The 64x48 capture is tests/test_gpu_track_res.py's (imported), quantised to a se
 units); the tracked sequence uses tests/test_gpu_online.py's scene (20 000 Gaussians, 320x240).  Everything is
 bitwise except the arrival rows, which carry tests/test_gpu_eval.py's allowance for frame_metrics against
 evaluate_literal (BOUND plus the literal's own distance from the float64 restatement on those very images)."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -252,21 +254,29 @@ def _same_sequences(a, b):
             assert torch.equal(x["im"], y["im"]) and torch.equal(x["depth"], y["depth"]), t
 
 
+@contextlib.contextmanager
+def _counted_resizes():
+    """The resize launches a capture makes while this is open (the list's length): resize_device as
+    splatam_amd.capture's _make_small reads it, wrapped."""
+    from splatam_amd import capture
+    calls = []
+    real = capture.resize_device
+    capture.resize_device = lambda *a, **k: (calls.append(1), real(*a, **k))[1]
+    try:
+        yield calls
+    finally:
+        capture.resize_device = real
+
+
 @pytest.fixture(scope="module")
 def given_raw(rawcap):
     """The raw-fed sequence with given poses: the first raw frame at construction, the others pushed with their
     odometry poses; the resize launches it made are counted."""
-    from splatam_amd import sequence as sq
-    calls = []
-    real = sq.resize_device
-    sq.resize_device = lambda *a, **k: (calls.append(1), real(*a, **k))[1]
-    try:
+    with _counted_resizes() as calls:
         seq = rawcap.sequence(rawcap.first_raw(), densify_mode="device", arrival_report=True)
         seq.frame(0)
         for t in range(1, N_RAW):
             assert seq.push_raw(*rawcap.raw[t], pose=rawcap.poses[t]) == t
-    finally:
-        sq.resize_device = real
     seq.check()
     torch.cuda.synchronize()
     return seq, len(calls)
@@ -277,8 +287,10 @@ def test_raw_sequence_with_given_poses(rawcap, given_raw):
     assert resize_calls == 0  # the ingest launch made every small frame: _make_small was not called
     fed = rawcap.sequence(rawcap.lit[:1], densify_mode="device")
     fed.frame(0)
-    for t in range(1, N_RAW):
-        assert fed.push(rawcap.lit[t]["im"], rawcap.lit[t]["depth"], w2c=rawcap.w2cs[t]) == t
+    with _counted_resizes() as fed_calls:
+        for t in range(1, N_RAW):
+            assert fed.push(rawcap.lit[t]["im"], rawcap.lit[t]["depth"], w2c=rawcap.w2cs[t]) == t
+    assert len(fed_calls) >= N_RAW - 1  # (the counter is live: a float frame's small frames are resize launches)
     fed.check()
     torch.cuda.synchronize()
     _same_sequences(seq, fed)
